@@ -7,10 +7,14 @@ on the R2R-canon model (H=768, 12 heads, 9 text + 2 pano + 4 cross-modal layers,
 36x768 view features, 80-token instructions, history 5, tasks cycled with the reference's 5:1:1:1:2:2 mix.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--prec bf16|fp32] [--task mix|sap|...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps once and reports them (`value`, `ms_per_step`);
+`--full` adds everything else the bench measures or checks: repeated regions, the batch sweep, the no-DCE and ragged steps, the
+exposed communication, the finite-state check, the roofline probes and kernel table, the one-rank exchange, the CPU oracle baseline
+and BASELINE configs 4 / 5.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -195,6 +199,29 @@ def cpu_baseline(budget_s=20.0, batch=16, max_steps=8):
                       f"{len(times)} steps, median of steps 2.. ({per_step:.2f} s/step)"}
 
 
+DUMP_SAMPLE = 1 << 20          # elements drawn from each 174.8 M-element arena for --dump-outputs (4 MiB each in float32)
+
+
+def dump_outputs(out_dir, loss, opt, moments=True):
+    """What the last timed step hands its caller, as float32 .npy files in `out_dir`: the step's loss (`loss.npy`) and the updated
+    fp32 master parameters; with `moments`, also AdamW's first and second moments (the step's gradients as the optimizer folded them
+    in).  The arenas are too large to write whole, so each file holds the same fixed, seeded sample of the flat arena: DUMP_SAMPLE
+    indices drawn from a CPU generator seeded with 0, sorted and de-duplicated (`param_sample.npy`, `exp_avg_sample.npy`,
+    `exp_avg_sq_sample.npy`).  About 12 MiB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = opt._flat_p.numel()
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(0)).unique()
+    idx_d = idx.to(opt._flat_p.device)
+    arrays = {"loss": loss.detach().float(), "param_sample": opt._flat_p[idx_d]}
+    if moments:
+        arrays["exp_avg_sample"] = opt._flat_m[idx_d]
+        arrays["exp_avg_sq_sample"] = opt._flat_v[idx_d]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    return sorted(arrays)
+
+
 def log(msg):
     if int(os.environ.get("RANK", 0)) == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -235,15 +262,21 @@ def main():
     ap.add_argument("--prec", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--task", default="mix", help="mix (5:1:1:1:2:2 cycle) or one of mlm/sap/sar/sprel/mrc/itm")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline K steps (the options below that name a probe, a "
+                    "region or a baseline act only with it): repeated regions, batch sweep, no-DCE and ragged steps, exposed communication, "
+                    "finite-state check, roofline probes, one-rank exchange, CPU oracle baseline, BASELINE configs 4 / 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss, "
+                    "a fixed seeded sample of the updated parameters and moments) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--no-probes", action="store_true", help="only the timed steps (for rocprofv3 runs: no probe launches in the kernel statistics)")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: no probes, only the timed regions (for rocprofv3 runs: no probe "
+                    "launches in the kernel statistics)")
     ap.add_argument("--ragged", action="store_true", help="headline run on ragged batches (SURVEY 8d: L ~ U[20, 80], T ~ U[0, 7] per sample, padded to the "
-                    "batch maximum as the reference's collate does) instead of full-length ones; without the flag the ragged variant is reported "
+                    "batch maximum as the reference's collate does) instead of full-length ones; without the flag, --full reports the ragged variant "
                     "next to `batch_sweep` as `ragged`")
-    ap.add_argument("--regions", type=int, default=3, help="timed regions of --steps steps each: the first is `value` (the contract's K steps), all of "
-                    "them are reported in `regions_ms_per_step` with their min / median")
-    ap.add_argument("--also-batch", type=int, default=-1, help="another per-GPU batch reported in `batch_sweep` (default: 16 -- the reference's "
+    ap.add_argument("--regions", type=int, default=3, help="with --full: timed regions of --steps steps each: the first is `value` (the K steps), "
+                    "all of them are reported in `regions_ms_per_step` with their min / median")
+    ap.add_argument("--also-batch", type=int, default=-1, help="with --full: another per-GPU batch reported in `batch_sweep` (default: 16 -- the reference's "
                     "per-GPU batch -- and 256 when --batch is left at 64 on one GPU; 0 = none)")
     ap.add_argument("--launch-check", action="store_true", help="plumbing check of the N-rank launch: rendezvous, one all-reduce, rank 0 prints "
                     "{\"launch_check\": true, \"n_gpus\": world}; no model, runs on a CPU-only host over gloo as well")
@@ -347,6 +380,7 @@ def main():
         get_batch(s)
     log("batches resident in HBM")
     gstep = [0]
+    last_loss = [None]                                  # the loss tensor of the latest step (--dump-outputs)
     use_graph = not args.no_graph
     graphed = None
     if use_graph:
@@ -362,13 +396,14 @@ def main():
             for g in opt.param_groups:
                 g["lr"] = lr
             key = (task, step % n_distinct, bsz) + _sfx()
-            graphed.step(key, b, task)
+            last_loss[0] = graphed.step(key, b, task)
             # the bench's inputs are resident in HBM: keep working on the captured step's own static input tensors (a
             # loader would write each new batch into them; GraphedTrainStep.step copies any other batch in)
             batches[key] = graphed.static_batch(key)
             return task, b["txt_ids"].shape[0]
         loss = net(b, task, True).mean()
         loss.backward()
+        last_loss[0] = loss
         if grad_sync is not None:
             grad_sync(opt)
         gstep[0] += 1
@@ -417,15 +452,18 @@ def main():
         return max_over_ranks(time.perf_counter() - t0, device), samples, flops
 
     dt, samples, flops = timed_region(args.batch, args.warmup, args.steps)
-    dead_main = sum_over_ranks(dead_sum[0], device)
     log(f"timed region: {dt:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:     # before anything else trains the model further
+        names = dump_outputs(args.dump_outputs, last_loss[0], opt, moments=not getattr(grad_sync, "sharded", False))
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
+    dead_main = sum_over_ranks(dead_sum[0], device)
     # the driver's K may be small (20 steps = 0.2 s): repeat the region so that box-to-box / run-to-run spread is visible
     regions = [dt / args.steps * 1e3]
-    for _ in range(max(0, args.regions - 1)):
+    for _ in range(max(0, args.regions - 1) if args.full else 0):
         dt_r, _, _ = timed_region(args.batch, 0, args.steps, verbose=False)
         regions.append(dt_r / args.steps * 1e3)
     exposed_comm_ms = None
-    if dist_on and not args.no_probes:
+    if dist_on and args.full and not args.no_probes:
         # the same steps with the collectives themselves skipped (every rank keeps its own values: timing only, after the measurement):
         # the difference is the part of the exchange that compute does not hide
         from vln_hamt_amd import parallel as par
@@ -463,17 +501,20 @@ def main():
             "mfma_roofline_frac_end_to_end": round(executed_flops / dt / world / 1e12 / PEAK_BF16_TFLOPS, 4),
             "mfma_roofline_frac_reference_work": round(total_flops / dt / world / 1e12 / PEAK_BF16_TFLOPS, 4),
             "hbm_peak_allocated_gb": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 1),
-            "exposed_comm_ms_per_step": exposed_comm_ms,
-            "regions_ms_per_step": [round(r, 3) for r in regions], "regions_min_ms": round(min(regions), 3),
-            "regions_median_ms": round(sorted(regions)[len(regions) // 2], 3),
-            # the timed steps trained a real model: every master parameter and both moments are finite afterwards (a NaN anywhere
-            # spreads within a few steps; NaN-filled operands also run at other clocks than real data, see DESIGN 4 on DVFS)
-            "state_finite_after_timed_region": bool(torch.isfinite(opt._flat_p).all() and torch.isfinite(opt._flat_m).all() and torch.isfinite(opt._flat_v).all()),
         }
+        if args.full:
+            out.update({
+                "exposed_comm_ms_per_step": exposed_comm_ms,
+                "regions_ms_per_step": [round(r, 3) for r in regions], "regions_min_ms": round(min(regions), 3),
+                "regions_median_ms": round(sorted(regions)[len(regions) // 2], 3),
+                # the timed steps trained a real model: every master parameter and both moments are finite afterwards (a NaN anywhere
+                # spreads within a few steps; NaN-filled operands also run at other clocks than real data, see DESIGN 4 on DVFS)
+                "state_finite_after_timed_region": bool(torch.isfinite(opt._flat_p).all() and torch.isfinite(opt._flat_m).all() and torch.isfinite(opt._flat_v).all()),
+            })
         # the other two per-GPU batches SURVEY 8d names next to the headline one -- 16 is the reference's own (pretrain_r2r.json:9) -- on
         # the same model / optimizer / number of steps
         also = [args.also_batch] if args.also_batch > 0 else ([16, 256] if (args.also_batch < 0 and args.batch == 64 and world == 1 and args.task == "mix") else [])
-        if also and world == 1 and not args.no_probes:
+        if args.full and also and world == 1 and not args.no_probes:
             out["batch_sweep"] = []
             for bsz in also:
                 dt2, smp2, fl2 = timed_region(bsz, args.warmup, args.steps if bsz <= 64 else max(12, args.steps // 2), verbose=False)
@@ -487,7 +528,7 @@ def main():
                 log(f"batch {bsz}: {dt2 / n2 * 1e3:.3f} ms/step")
                 for k in [k for k in batches if k[2] == bsz]:
                     del batches[k]
-        if _vil.DEAD_SIDE_ELIMINATION and not args.no_probes and world == 1:
+        if args.full and _vil.DEAD_SIDE_ELIMINATION and not args.no_probes and world == 1:
             # the same step with EVERY launch of the reference's forward (the unread side / rows of the last cross-modal layer included)
             full_mode[0] = True
             _vil.DEAD_SIDE_ELIMINATION = False
@@ -502,7 +543,7 @@ def main():
             log(f"full work (no dead-code elimination): {dt4 / n4 * 1e3:.3f} ms/step")
             for k in [k for k in batches if k[-1] == "full"]:
                 del batches[k]
-        if not args.ragged and not args.no_probes and args.task == "mix" and world == 1:
+        if args.full and not args.ragged and not args.no_probes and args.task == "mix" and world == 1:
             # SURVEY 8d's ragged variant: per-sample L ~ U[20, 80], T ~ U[0, 7], padded to the batch maximum (the reference's collate);
             # throughput in samples/s, FLOPs counted at every sample's OWN lengths (padding is work the path does, not work it is credited for)
             ragged_mode[0] = True
@@ -515,16 +556,18 @@ def main():
             ragged_mode[0] = False
             for k in [k for k in batches if k[-1] == "ragged"]:
                 del batches[k]
-        if args.task == "mix":
+        if not (args.full and not args.no_probes):
+            cycle = None
+        elif args.task == "mix":
             cycle = [get_batch(s_) for s_ in range(len(sched.cycle))]
         else:
             cycle = [get_batch(0)]
-        if dist_on:
+        if dist_on and args.full:
             # the probes below run model passes on THIS rank only: a gradient exchange they started would wait for ranks that sit
             # in the final barrier.  (Found with a 2-rank run at the end of round 2: the bench hung here for any N > 1.)
             from vln_hamt_amd import parallel as par
             par.DRY[0] = True
-        if not args.no_probes:
+        if args.full and not args.no_probes:
             from tools import roofline_probe as rp
             table = rp.kernel_table(model, opt, cycle, device, live=not dist_on)
             dom = dict(table[0])                            # the kernel with the largest share of a step
@@ -547,7 +590,7 @@ def main():
             out["box"] = box_probe(device)
             out["roofline_subblock_xattn"] = rp.subblock_xattn(model, args.batch, device)
             out["roofline_probe_xattn"] = time_xattn_probe(args.batch, device)
-        if world == 1 and not dist_on and not args.no_probes and graphed is not None and args.prec == "bf16" and args.task == "mix":
+        if args.full and world == 1 and not dist_on and not args.no_probes and graphed is not None and args.prec == "bf16" and args.task == "mix":
             # What the multi-GPU step's machinery costs before a byte moves: the same steps through the sharded exchange
             # (parallel.ShardedGradSync: launch groups on two lanes, wire staging, reduce-scatter / owned-slice AdamW / all-gather
             # calls, the eager section between the graphs) with a ONE-rank RCCL group, against the plain single-GPU step above.
@@ -567,16 +610,17 @@ def main():
             except Exception as e:      # a measurement aid must never cost the bench line
                 out["exchange_overhead_ms_world1"] = None
                 log(f"one-rank exchange probe failed: {type(e).__name__}: {e}")
-        log("roofline probes done; timing the CPU oracle baseline")
-        if world == 1 and not args.no_cpu_baseline and not args.no_probes:
+        if args.full:
+            log("roofline probes done; timing the CPU oracle baseline")
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.no_probes:
             out["cpu_baseline"] = cpu_baseline(args.cpu_budget)
             # SURVEY 8d names two CPU cases: B = 16 (above: the reference's per-GPU batch) and B = 2 (BASELINE config 1, the reference's
             # own CPU-runnable plumbing case)
             b2 = cpu_baseline(min(8.0, args.cpu_budget), batch=2, max_steps=10)
             out["cpu_baseline"]["batch2"] = {"value": b2["value"], "unit": b2["unit"], "sample": b2["sample"]}
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
-        if world == 1 and not dist_on and not args.no_probes and args.task == "mix" and args.prec == "bf16" and not os.environ.get("HAMT_BENCH_NO_EXTRA"):
+        if args.full and world == 1 and not dist_on and not args.no_probes and args.task == "mix" and args.prec == "bf16" and not os.environ.get("HAMT_BENCH_NO_EXTRA"):
             # BASELINE configs 4 and 5 on this GPU, driver-visible (VERDICT r3 missing 6): measurement aids behind the headline -- they build
             # their own models and must never cost the bench line
             for key, mod, kw in (("e2e_image_step", "e2e_bench", dict(B=1, steps=12, use_graph=True)),

@@ -404,7 +404,7 @@ def test_gradient_norm_tracks_gradients_changed_after_the_pass(tiny):
 
 @pytest.mark.parametrize("sharded", ["1", "0"])
 def test_two_rank_bench_with_probes_finishes(tmp_path, sharded):
-    """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, default probes) must print its JSON line and exit:
+    """`bench.py --gpus 2 --full` under torch.distributed.run (and run plainly) must print its JSON line and exit:
     rank 0 runs the roofline probes -- model passes of its own -- while the other ranks wait in the final barrier, so the probes
     must not start a gradient exchange (round 2: they did, and every N > 1 run hung behind the timed region).  Two ranks on the
     one GPU over gloo (RCCL refuses two ranks per device); the numbers mean nothing here, finishing does."""
@@ -415,14 +415,41 @@ def test_two_rank_bench_with_probes_finishes(tmp_path, sharded):
         port = s_.getsockname()[1]
     env = dict(os.environ, HAMT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", HAMT_SHARDED=sharded)   # reduce-scatter / all-reduce exchange
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "8"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "8", "--full"]
     if sharded == "1":      # ... and run plainly, the way the driver runs `--gpus 1`: bench.py starts its own ranks (a child process, before any GPU call)
-        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "8"]
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "8", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["roofline"]["frac"] > 0 and out["state_finite_after_timed_region"] is True, line[:600]
+
+
+def test_plain_bench_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run does the headline only -- set up, warm up, exactly --steps timed steps, the JSON line -- and
+    `--dump-outputs DIR` writes what the last timed step computed (bench.dump_outputs): float32 .npy files, finite, under 64 MB."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "8",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "bf16", out
+    assert out["higher_is_better"] is True and out["unit"] == "panorama-steps/s" and out["metric"], out
+    extras = {"regions_ms_per_step", "state_finite_after_timed_region", "batch_sweep", "full_work", "ragged", "roofline",
+              "kernel_table", "box", "cpu_baseline", "e2e_image_step", "rollout_step", "exchange_overhead_ms_world1"}
+    assert not extras & set(out), sorted(extras & set(out))          # (behind --full)
+    names = sorted(os.listdir(out_dir))
+    assert names == ["exp_avg_sample.npy", "exp_avg_sq_sample.npy", "loss.npy", "param_sample.npy"], names
+    assert sum(os.path.getsize(out_dir / n) for n in names) <= 64 << 20
+    for n in names:
+        a = np.load(out_dir / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+    assert np.load(out_dir / "param_sample.npy").size > 1000
+    assert float(np.load(out_dir / "exp_avg_sq_sample.npy").max()) > 0        # the moments have seen gradients
 
 
 def test_role_streams_are_pairwise_distinct():

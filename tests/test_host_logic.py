@@ -84,3 +84,25 @@ def test_range_finality_and_static_cuts():
     assert fa[0][2] == 0 and fa[-1][2] == 3 and fb[0][2] == 1
     for lo, hi, after, touched in fa:
         assert after == max(touched)
+
+
+
+def test_bench_dump_outputs_is_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: the loss and the same seeded, sorted sample of the flat parameter / moment arenas on every call, as
+    float32 .npy files -- two builds of the project compare output for output."""
+    import types
+    import numpy as np
+    import bench
+    n = 3 * bench.DUMP_SAMPLE
+    g = torch.Generator().manual_seed(5)
+    opt = types.SimpleNamespace(_flat_p=torch.randn(n, generator=g), _flat_m=torch.randn(n, generator=g), _flat_v=torch.rand(n, generator=g))
+    loss = torch.tensor(2.5)
+    assert bench.dump_outputs(str(tmp_path / "a"), loss, opt) == ["exp_avg_sample", "exp_avg_sq_sample", "loss", "param_sample"]
+    assert bench.dump_outputs(str(tmp_path / "b"), loss, opt, moments=False) == ["loss", "param_sample"]
+    idx = torch.randint(0, n, (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique()
+    for name, ref in (("param_sample", opt._flat_p[idx]), ("exp_avg_sample", opt._flat_m[idx]), ("exp_avg_sq_sample", opt._flat_v[idx])):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, ref.numpy()), name
+    assert np.array_equal(np.load(tmp_path / "b" / "param_sample.npy"), np.load(tmp_path / "a" / "param_sample.npy"))
+    assert float(np.load(tmp_path / "a" / "loss.npy")) == 2.5
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["loss.npy", "param_sample.npy"]

@@ -1,5 +1,6 @@
 """Pin the CPU oracle against vectors captured from the real reference (oracle/gen_goldens.py)."""
 import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -7,6 +8,7 @@ import torch
 
 from oracle.hamt_oracle import (HamtOracle, OracleConfig, adamw_step, clip_grad_norm, decays, lr_at,
                                 make_state_dict, navcmt_param_shapes, pretrain_param_shapes)
+from oracle.ref_shim import REF as REFERENCE_TREE
 from vln_hamt_amd.synth import make_batch
 
 from _util import batch_from, load_npz, sub, tiny_cfg
@@ -175,7 +177,8 @@ def test_oracle_matches_reference_at_the_benchmarked_batch():
         np.testing.assert_allclose(grad_probe(g, probes.shape[1]), probes[i], rtol=0, atol=2e-5 * max(1.0, float(np.abs(probes[i]).max())), err_msg=k)
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference"), reason="needs the reference tree (build container only)")
+@pytest.mark.skipif(not os.path.isdir(REFERENCE_TREE), reason="needs the reference's source tree (HAMT_REFERENCE), which the repository "
+                    "does not hold")
 def test_committed_tiny_goldens_match_their_generator(tmp_path, monkeypatch):
     """Generator <-> fixture drift guard: re-running oracle/gen_goldens.py's tiny set against the real reference
     must reproduce the committed file key for key and bit for bit."""
