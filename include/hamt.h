@@ -469,6 +469,21 @@ int hamt_sumsq_partials(size_t n, const float* partials, float* out, int accumul
  * of element 0): the widening of a reduce-scattered bf16 gradient chunk and its share of the global norm in one pass. */
 int hamt_wire_unpack_sumsq(size_t first, size_t n, const void* y16, float* g, const int* ends, const float* hyp, int nparams,
                            float* out, int accumulate, float* ws, void* stream);
+/* Ralamb / RangerLars (pretrain_src/optim/ralamb.py, lookahead.py): three launches over the arenas (moments + per-item partial sums of
+ * squares, per-parameter trust ratio, update + Lookahead sync + bf16 shadow).  Deterministic: no float atomics, fixed summation order.
+ * items (DEVICE, int32, 2 * nitems + nparams + 2 entries): [0, nitems] float4 start offset of every item (entry nitems = end of the
+ *   last one), [nitems + 1, 2 * nitems] the parameter of every item, [2 * nitems + 1, 2 * nitems + nparams + 1] the first item of
+ *   every parameter (last entry = nitems).  Items lie in arena order inside one parameter each, at most 1024 float4 long.
+ * hyp: the hamt_adamw_table table, {lr, s*lr (RAdam step size times lr), weight_decay, active}; only columns 1 and 3 are read.
+ * rl (DEVICE, nparams x 4 floats): {N_sma >= 5 (1 / 0), Lookahead action (0 none, 1 create the slow weights, 2 interpolate), alpha,
+ *   -weight_decay*lr}.  partials: 2 floats per item (scratch).  stats (DEVICE, nparams x 4 floats): {weight_norm, adam_norm,
+ *   trust_ratio, 0} of every active parameter after the call (inactive rows are left as they are).
+ * Parameters with active == 0 are not touched at all (p, g, m, v, slow, p16, stats).  slow may be NULL (no Lookahead: every action
+ * is then ignored); p16 may be NULL.  g is zeroed where active == 1 and zero_grad != 0. */
+int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p16, float* slow, const int* items, int nitems,
+                      const float* hyp, const float* rl, int nparams, float* partials, float* stats, const float* gnorm_sq,
+                      float max_norm, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                      int zero_grad, void* stream);
 /* g *= min(1, max_norm / (sqrt(*gnorm_sq) + 1e-6))  -- standalone clip for torch-optimiser users */
 int hamt_clip_scale(size_t n, float* g, const float* gnorm_sq, float max_norm, void* stream);
 

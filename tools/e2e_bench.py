@@ -2,8 +2,9 @@
 """Image-input pretrain step (BASELINE config 4 "end-to-end pretrain", one GPU): raw 224x224 views -> ViT-B/16 backbone
 (T*36 panorama views no-grad, T history views + 36 observation views with gradient) -> HAMT trunk -> loss -> backward
 -> clip 5.0 -> flat AdamW over all 261 M parameters.  The reference runs this at train_batch_size 1, max_txt_len 60
-(pretrain_r2r_e2e.json) with the 5:1:1:1:2:2 task mix; its Ralamb+Lookahead optimiser is outside the hot-path scope,
-AdamW stands in.  usage: e2e_bench.py [batch=2] [steps=12] [graph]   (graph: whole-step hipGraph replay per task)
+(pretrain_r2r_e2e.json) with the 5:1:1:1:2:2 task mix and its own optimiser, RangerLars (Ralamb + Lookahead): `rangerlars`
+runs the step with it (optim.rangerlars), the default stays AdamW.
+usage: e2e_bench.py [batch=2] [steps=12] [graph|eager] [adamw|rangerlars]   (graph: whole-step hipGraph replay per task)
 bench.py imports `run` for its `e2e_image_step` key."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,11 +23,11 @@ def _trunk_fwd(task):
     return f + (5 if task == "itm" else 1) * 4 * xl(L, T + 1 + (V + 1 if ob else 0))
 
 
-def run(B=1, steps=12, use_graph=True, dev=None, verbose=False):
+def run(B=1, steps=12, use_graph=True, dev=None, verbose=False, optim="adamw"):
     from vln_hamt_amd import ops
     from vln_hamt_amd.model.image_pretrain import MultiStepNavImagePreTraining
     from vln_hamt_amd.modeling import HamtConfig
-    from vln_hamt_amd.optim import AdamW, clip_grad_norm_
+    from vln_hamt_amd.optim import AdamW, RangerLars, clip_grad_norm_
     from vln_hamt_amd.optim.misc import NO_DECAY
     from vln_hamt_amd.parallel import TaskSchedule
     from vln_hamt_amd.synth import make_batch, make_itm_rng
@@ -36,8 +37,9 @@ def run(B=1, steps=12, use_graph=True, dev=None, verbose=False):
     model = MultiStepNavImagePreTraining(cfg).to(dev).train()
     named = list(model.named_parameters())
     n_par = sum(p.numel() for _, p in named)
-    opt = AdamW([{"params": [p for n, p in named if not any(nd in n for nd in NO_DECAY)], "weight_decay": 0.01},
-                 {"params": [p for n, p in named if any(nd in n for nd in NO_DECAY)], "weight_decay": 0.0}], lr=5e-5, betas=(0.9, 0.98))
+    opt = {"adamw": AdamW, "rangerlars": RangerLars}[optim](
+        [{"params": [p for n, p in named if not any(nd in n for nd in NO_DECAY)], "weight_decay": 0.01},
+         {"params": [p for n, p in named if any(nd in n for nd in NO_DECAY)], "weight_decay": 0.0}], lr=5e-5, betas=(0.9, 0.98))
     opt.materialize()
     sched = TaskSchedule(cyclic=True)
     g = torch.Generator(device=dev); g.manual_seed(3)
@@ -94,7 +96,8 @@ def run(B=1, steps=12, use_graph=True, dev=None, verbose=False):
     dt = time.perf_counter() - t0
     finite = bool(torch.isfinite(opt._flat_p).all())
     out = {"workload": "BASELINE config 4: image-input pretrain step -- ViT-B/16 over raw 224x224 views (T*36 panorama views no-grad, T history + 36 "
-                       "observation views with gradient) + the feature-input trunk, six-task mix, fwd + bwd + clip + AdamW over all parameters, dropout 0.1",
+                       f"observation views with gradient) + the feature-input trunk, six-task mix, fwd + bwd + clip + {type(opt).__name__} over all "
+                       "parameters, dropout 0.1",
            "per_gpu_batch": B, "txt_len": L, "hist_len": T, "views": V, "parameters_M": round(n_par / 1e6, 1), "steps": steps,
            "ms_per_step": round(dt / steps * 1e3, 2), "value": round(n_pano / dt, 2), "unit": "panorama-steps/s",
            "no_grad_views_per_s": round(n_pano * T * V / dt, 0), "launch": "hipGraph replay" if use_graph else "eager",
@@ -112,5 +115,6 @@ if __name__ == "__main__":
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 12
     use_graph = len(sys.argv) > 3 and sys.argv[3] == "graph"
+    optim = sys.argv[4] if len(sys.argv) > 4 else "adamw"
     import json
-    print(json.dumps(run(B, steps, use_graph, verbose=True), indent=1))
+    print(json.dumps(run(B, steps, use_graph, verbose=True, optim=optim), indent=1))

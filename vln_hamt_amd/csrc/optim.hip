@@ -410,3 +410,180 @@ extern "C" int hamt_clip_scale(size_t n, float* g, const float* gnorm_sq, float 
   HAMT_CHECK_LAUNCH("hamt_clip_scale");
   return HAMT_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Ralamb (RAdam + a LARS-style per-tensor trust ratio, pretrain_src/optim/ralamb.py) with the Lookahead wrapper (lookahead.py), as
+// three static launches over the flat arenas:
+//   1. ralamb_moments_kernel: m, v of every active element (clip fused as in adamw_table_kernel; gradient slot zeroed where the table
+//      says so) and, per ITEM, the two partial sums  sum(p_dec^2)  and  sum((p_dec - s*lr*u)^2)  -- the decayed weights and the
+//      candidate weights whose norms make the trust ratio (ralamb.py:70-82);
+//   2. ralamb_trust_kernel: per parameter, its items' partials summed in a fixed order -> {weight_norm, adam_norm, trust};
+//   3. ralamb_apply_kernel: p = p_dec - (s*lr*trust)*u, recomputed from p, m, v; the Lookahead sync (create / interpolate the slow
+//      weights) of this step; the bf16 shadow from the final value.
+// Items: a static host-built table, each item inside one parameter and at most one 16-KiB chunk (256 threads x 4 float4), in arena
+// order, each with its own partial slot.  The grid sweeps the items together (block b: items b, b + gridDim, ...), the access
+// pattern of adamw_table_kernel; every partial is a block reduction of a fixed shape, so the sums (and everything after them) are
+// bit-identical from launch to launch and independent of the grid size.  No float atomics.
+// Traffic per element: pass 1 reads p, g, m, v and writes m, v (24 B; + 4 B where the gradient slot is zeroed), pass 3 reads p, m, v and
+// writes p and the bf16 shadow (18 B; + 8 B for the slow weights on a Lookahead sync).
+namespace {
+
+constexpr int RL_U = 4;     // float4 per thread per item: items are at most 256 * RL_U float4
+
+struct RalambCoef {
+  float coef, b1, b2, omb1, omb2, eps;
+};
+
+// The reference's statements in its own operation order (torch CPU kernels): mul_ then add_(alpha) = fma, addcmul_ = self + (value*t1)*t2,
+// add_(p, alpha) = fma, addcdiv_ = self + (value*t1)/t2.  Contraction off, so that nothing else is fused.
+__device__ __forceinline__ void ralamb_moments(float p, float g, float& m, float& v, const RalambCoef& c, float dec, float nslr, bool rect,
+                                               float& pd, float& cand) {
+#pragma clang fp contract(off)
+  const float gg = g * c.coef;
+  m = fmaf(gg, c.omb1, m * c.b1);                   // exp_avg.mul_(b1).add_(grad, alpha=1-b1)               ralamb.py:47
+  v = v * c.b2 + (c.omb2 * gg) * gg;                // exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1-b2)  ralamb.py:49
+  pd = dec != 0.f ? fmaf(p, dec, p) : p;            // p.add_(p, alpha=-wd*lr), BEFORE the norms              ralamb.py:70-71
+  cand = rect ? pd + (nslr * m) / (sqrtf(v) + c.eps) // radam_step = p_dec - s*lr*m/(sqrt(v)+eps)             ralamb.py:74-79
+              : fmaf(m, nslr, pd);                  //             p_dec - s*lr*m  (N_sma < 5)
+}
+__device__ __forceinline__ float ralamb_new_p(float p, float m, float v, float eps, float dec, float c, bool rect) {
+#pragma clang fp contract(off)
+  const float pd = dec != 0.f ? fmaf(p, dec, p) : p;
+  return rect ? pd + (c * m) / (sqrtf(v) + eps) : fmaf(m, c, pd);      // ralamb.py:92-95
+}
+
+__global__ __launch_bounds__(256) void ralamb_moments_kernel(const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, const int* __restrict__ items, int nitems,
+                                                             const float4* __restrict__ hyp, const float4* __restrict__ rl,
+                                                             const float* __restrict__ gnorm_sq, float max_norm, float b1, float b2,
+                                                             float omb1, float omb2, float eps, int zero_grad, float2* __restrict__ partials) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const RalambCoef c{clip_coef(gnorm_sq, max_norm), b1, b2, omb1, omb2, eps};
+  const int* item_param = items + nitems + 1;
+  __shared__ float red[2][4][2];
+  int par = 0;
+  for (int j = blockIdx.x; j < nitems; j += gridDim.x) {
+    const int q = item_param[j];
+    const float4 h = hyp[q];
+    if (h.w == 0.f) continue;                       // (uniform over the block: no barrier is skipped by part of it)
+    const float4 r = rl[q];                         // {N_sma >= 5, Lookahead action, alpha, -wd*lr}
+    const size_t lo = (size_t)items[j], hi = (size_t)items[j + 1];
+    const bool zg = zero_grad && h.w == 1.f, rect = r.x != 0.f;
+    const float nslr = -h.y;
+    float sa = 0.f, sb = 0.f;
+    f4 P[RL_U], G[RL_U], M[RL_U], V[RL_U];
+#pragma unroll
+    for (int u = 0; u < RL_U; ++u) {
+      const size_t i = lo + threadIdx.x + (size_t)u * 256;
+      if (i < hi) { P[u] = ((const f4*)p)[i]; G[u] = ((const f4*)g)[i]; M[u] = ((const f4*)m)[i]; V[u] = ((const f4*)v)[i]; }
+    }
+#pragma unroll
+    for (int u = 0; u < RL_U; ++u) {
+      const size_t i = lo + threadIdx.x + (size_t)u * 256;
+      if (i < hi) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float mm = M[u][k], vv = V[u][k], pd, cand;
+          ralamb_moments(P[u][k], G[u][k], mm, vv, c, r.w, nslr, rect, pd, cand);
+          M[u][k] = mm; V[u][k] = vv;
+          sa += pd * pd;
+          sb += cand * cand;
+        }
+        __builtin_nontemporal_store(M[u], (f4*)m + i);
+        __builtin_nontemporal_store(V[u], (f4*)v + i);
+        if (zg) __builtin_nontemporal_store((f4){0.f, 0.f, 0.f, 0.f}, (f4*)g + i);
+      }
+    }
+    sa = wave_sum(sa);
+    sb = wave_sum(sb);
+    if ((threadIdx.x & 63) == 0) { red[par][threadIdx.x >> 6][0] = sa; red[par][threadIdx.x >> 6][1] = sb; }
+    __syncthreads();                                // (two LDS buffers: the next item's writes cannot overtake this read)
+    if (threadIdx.x == 0)
+      partials[j] = make_float2((red[par][0][0] + red[par][1][0]) + (red[par][2][0] + red[par][3][0]),
+                                (red[par][0][1] + red[par][1][1]) + (red[par][2][1] + red[par][3][1]));
+    par ^= 1;
+  }
+}
+
+// one wave per parameter: its items' partials in a fixed order (lane l: items l, l + 64, ...; then the fixed butterfly)
+__global__ __launch_bounds__(256) void ralamb_trust_kernel(const int* __restrict__ items, int nitems, const float4* __restrict__ hyp, int nparams,
+                                                           const float2* __restrict__ partials, float4* __restrict__ stats) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (q >= nparams || hyp[q].w == 0.f) return;      // inactive: its last statistics stay (the reference keeps them in its state)
+  const int* first = items + 2 * nitems + 1;
+  float a = 0.f, b = 0.f;
+  for (int j = first[q] + lane; j < first[q + 1]; j += 64) { const float2 t = partials[j]; a += t.x; b += t.y; }
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if (lane == 0) {
+    const float ws = sqrtf(a), an = sqrtf(b);
+    const float wn = ws > 10.f ? 10.f : ws;         // .clamp(0, 10) (a NaN stays a NaN)   ralamb.py:82
+    const float tr = (wn == 0.f || an == 0.f) ? 1.f : wn / an;                               // ralamb.py:83-86
+    stats[q] = make_float4(wn, an, tr, 0.f);
+  }
+}
+
+__global__ __launch_bounds__(256) void ralamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                           bf16_t* __restrict__ p16, float* __restrict__ slow, const int* __restrict__ items,
+                                                           int nitems, const float4* __restrict__ hyp, const float4* __restrict__ rl,
+                                                           const float4* __restrict__ stats, float eps) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const int* item_param = items + nitems + 1;
+  for (int j = blockIdx.x; j < nitems; j += gridDim.x) {
+    const int q = item_param[j];
+    const float4 h = hyp[q];
+    if (h.w == 0.f) continue;
+    const float4 r = rl[q];
+    const size_t lo = (size_t)items[j], hi = (size_t)items[j + 1];
+    const bool rect = r.x != 0.f;
+    const int act = slow ? (int)r.y : 0;            // 1: create the slow weights (= the new weights), 2: slow += alpha (p - slow), p = slow
+    const float cs = -(h.y * stats[q].z);           // -s*lr*trust_ratio (ralamb.py:92-95)
+    f4 P[RL_U], M[RL_U], V[RL_U], S[RL_U];
+#pragma unroll
+    for (int u = 0; u < RL_U; ++u) {
+      const size_t i = lo + threadIdx.x + (size_t)u * 256;
+      if (i < hi) {
+        P[u] = ((const f4*)p)[i]; M[u] = ((const f4*)m)[i]; V[u] = ((const f4*)v)[i];
+        if (act == 2) S[u] = ((const f4*)slow)[i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < RL_U; ++u) {
+      const size_t i = lo + threadIdx.x + (size_t)u * 256;
+      if (i < hi) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float pn = ralamb_new_p(P[u][k], M[u][k], V[u][k], eps, r.w, cs, rect);
+          if (act == 2) pn = fmaf(pn - S[u][k], r.z, S[u][k]);      // slow.add_(alpha, fast - slow); fast.copy_(slow)   lookahead.py:37-39
+          P[u][k] = pn;
+        }
+        __builtin_nontemporal_store(P[u], (f4*)p + i);
+        if (act) __builtin_nontemporal_store(P[u], (f4*)slow + i);
+        if (p16) ((uint2*)p16)[i] = make_uint2(pack_bf2(P[u][0], P[u][1]), pack_bf2(P[u][2], P[u][3]));
+      }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p16, float* slow, const int* items, int nitems,
+                                 const float* hyp, const float* rl, int nparams, float* partials, float* stats, const float* gnorm_sq,
+                                 float max_norm, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                 int zero_grad, void* stream) {
+  HAMT_CHECK_ARG(p && g && m && v && items && hyp && rl && partials && stats && nitems > 0 && nparams > 0, "hamt_ralamb_table: bad argument");
+  HAMT_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                 ((uintptr_t)slow % 16) == 0 && ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)rl % 16) == 0 &&
+                 ((uintptr_t)stats % 16) == 0 && ((uintptr_t)partials % 8) == 0,
+                 "hamt_ralamb_table: arenas / tables must be 16-byte aligned (partials 8)");
+  hipStream_t s = as_stream(stream);
+  const int nb = nitems < 2048 ? nitems : 2048;     // (the grid sweeps the items together: see adamw_table_kernel)
+  hipLaunchKernelGGL(ralamb_moments_kernel, dim3(nb), dim3(256), 0, s, p, g, m, v, items, nitems, (const float4*)hyp, (const float4*)rl,
+                     gnorm_sq, max_norm, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, zero_grad, (float2*)partials);
+  hipLaunchKernelGGL(ralamb_trust_kernel, dim3((nparams + 3) / 4), dim3(256), 0, s, items, nitems, (const float4*)hyp, nparams,
+                     (const float2*)partials, (float4*)stats);
+  hipLaunchKernelGGL(ralamb_apply_kernel, dim3(nb), dim3(256), 0, s, p, m, v, (bf16_t*)p16, slow, items, nitems, (const float4*)hyp,
+                     (const float4*)rl, (const float4*)stats, eps);
+  HAMT_CHECK_LAUNCH("hamt_ralamb_table");
+  return HAMT_OK;
+}

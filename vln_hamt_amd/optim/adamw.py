@@ -162,6 +162,10 @@ class AdamW(Optimizer):
         if not 0.0 <= eps:
             raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias))
+        self._init_host_state()
+
+    def _init_host_state(self):
+        """the host-side bookkeeping of the arenas (shared with optim.rangerlars.Ralamb, whose defaults differ)"""
         self._built = False
         self._pending_clip = None   # (gnorm_sq device scalar, max_norm)
         self._packed = False

@@ -360,13 +360,21 @@ def shardable(optimizer, world: int) -> bool:
     return o._n % (8 * world) == 0 and o._n_shadow_only % (8 * world) == 0
 
 
+def per_tensor_update(optimizer) -> bool:
+    """Does the optimizer's update need every parameter's whole norm (optim.rangerlars: the trust ratio)?  The sharded exchange
+    updates owned slices that cut through parameters: such an optimizer takes the all-reduce exchange."""
+    from .optim.rangerlars import Ralamb
+    return isinstance(optimizer, Ralamb)
+
+
 def make_grad_sync(optimizer, prec: str = "bf16", n_groups: int = 4, wire: str | None = None, sharded: bool | None = None):
     """The gradient exchange for this process group: ShardedGradSync (reduce-scatter, owned-slice AdamW, all-gather) in bf16 mode
-    when the arenas split evenly over the ranks, else OverlappedGradSync (all-reduce, full AdamW on every rank)."""
+    when the arenas split evenly over the ranks, else OverlappedGradSync (all-reduce, full AdamW on every rank).  A RangerLars
+    always gets OverlappedGradSync (per_tensor_update)."""
     wire = wire or default_wire(prec)
     world = dist.get_world_size() if dist.is_initialized() else 1
     if sharded is None:
-        sharded = os.environ.get("HAMT_SHARDED", "1") != "0" and prec == "bf16"
+        sharded = os.environ.get("HAMT_SHARDED", "1") != "0" and prec == "bf16" and not per_tensor_update(optimizer)
     if sharded and not shardable(optimizer, world):
         import warnings
         warnings.warn(f"vln_hamt_amd.parallel: 8 x world size ({world}) does not divide the arena regions (multiples of 512 elements); "
@@ -397,6 +405,9 @@ class ShardedGradSync(OverlappedGradSync):
     sharded = True
 
     def __init__(self, optimizer, n_groups: int = 4, wire: str = "fp32"):
+        if per_tensor_update(optimizer):
+            raise ValueError(f"ShardedGradSync: {type(optimizer).__name__} needs each parameter's whole norm for its trust ratio, the owned "
+                             "slices cut through parameters; use the all-reduce exchange (OverlappedGradSync, which make_grad_sync picks)")
         super().__init__(optimizer, n_groups, wire)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
