@@ -64,9 +64,11 @@ int hamt_last_kernel(char* buf, size_t n);
  *   HAMT_WS_LNRED_TABLE  {n}        hamt_ln_bwd_reduce_grouped `table`
  *   HAMT_WS_VIS_EMBED_BWD {M, H}    hamt_vis_embed_bwd `ws`
  *   HAMT_WS_EMBED_BWD     {R, H}    hamt_embed_sum_bwd `ws`
+ *   HAMT_WS_OBJ_EMBED_BWD {M, H}    hamt_obj_embed_bwd `ws`
  * returns the size in bytes, or 0 for an unknown op / malformed shape */
 enum { HAMT_WS_GEMM_SPLITK = 0, HAMT_WS_COLSUM = 1, HAMT_WS_SUMSQ = 2, HAMT_WS_LN_BWD = 3, HAMT_WS_WGRAD_TABLE = 4, HAMT_WS_LNRED_TABLE = 5, HAMT_WS_VIS_EMBED_BWD = 6,
-       HAMT_WS_EMBED_BWD = 7 /* {R, H}: hamt_embed_sum_bwd `ws` = max(HAMT_WS_COLSUM {R, H}, 136 R bytes) */ };
+       HAMT_WS_EMBED_BWD = 7 /* {R, H}: hamt_embed_sum_bwd `ws` = max(HAMT_WS_COLSUM {R, H}, 136 R bytes) */,
+       HAMT_WS_OBJ_EMBED_BWD = 8 };
 size_t hamt_workspace_bytes(int op, const int* shape, int nshape);
 
 /* ------------------------------------------------------------------------------------------------
@@ -265,6 +267,47 @@ int hamt_vis_embed_bwd(const hamt_vis_embed_desc* d, const float* dy, const void
                        const float* b_ang, const float* gamma_img, const float* gamma_ang, const float* stats, float* dx, void* dx16,
                        float* dgamma_img, float* dbeta_img, float* dgamma_ang, float* dbeta_ang, float* db_ang, float* dw_ang,
                        float* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * obj_embed: REVERIE's object embedding (finetune reverie/vlnbert_navref.py:31-42), per object row
+ *     y = dropout( LN_out( LN_img(x1) + LN_ang(ang W_ang^T + b_ang) + LN_pos(pos W_pos^T + b_pos) + nav + tt ) )
+ *   x1 [M, H] = img_linear's output (bf16 or fp32); ang [M, 4] / pos [M, 5] fp32 with row strides ld_ang / ld_pos (any; read
+ *   element by element); w_ang [H, 4], w_pos [H, 5] (nn.Linear layout); tt / nav = ONE row each (token_type_embeddings row 1,
+ *   nav_type_embedding row 2), added to every object.  Every parameter pointer 16-byte aligned.  Dropout (p_drop) after the
+ *   output LayerNorm uses the counter-based mask of hamt_ln_fwd's p_post under (rng, call_id); nothing is stored.
+ * fwd: y [M, H] fp32; stats [8][M] = mean / rstd of the image, angle, position and output LayerNorms (for backward).
+ * bwd: dy [M, H] -> dx = d(x1) as fp32 [M, H] and / or dx16 = its bf16 image [Mpad16, H] (rows [M, Mpad16) zero); the branch
+ *   activations are recomputed from x1 / ang / pos.  Every parameter gradient is ADDED to its destination in `g` (a NULL
+ *   destination is skipped); dtt and dnav (the two constant rows) both receive the column sum of d(LN_out input).  Per-block
+ *   partials in ws (HAMT_WS_OBJ_EMBED_BWD {M, H} bytes) are summed in a fixed order: bit-reproducible, no atomics.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int M, H;
+  int A;      /* angle features: 4 (the only size built) */
+  int ld_ang; /* row stride of ang, in floats */
+  int P;      /* position features: 5 (the only size built) */
+  int ld_pos; /* row stride of pos, in floats */
+  float eps_img, eps_ang, eps_pos, eps_out;
+  float p_drop;
+  uint32_t call_id;
+  int x_bf16; /* x1 is bf16 (else fp32) */
+  int Mpad16; /* rows of the optional bf16 image dx16 (0: none beyond M) */
+} hamt_obj_embed_desc;
+typedef struct {
+  const float *w_ang, *b_ang, *w_pos, *b_pos;
+  const float *gamma_img, *beta_img, *gamma_ang, *beta_ang, *gamma_pos, *beta_pos;
+  const float *tt, *nav, *gamma_out, *beta_out;
+} hamt_obj_embed_params;
+typedef struct {
+  float *dw_ang, *db_ang, *dw_pos, *db_pos;
+  float *dgamma_img, *dbeta_img, *dgamma_ang, *dbeta_ang, *dgamma_pos, *dbeta_pos;
+  float *dtt, *dnav, *dgamma_out, *dbeta_out;
+} hamt_obj_embed_grads;
+int hamt_obj_embed_fwd(const hamt_obj_embed_desc* d, const hamt_obj_embed_params* p, const void* x1, const float* ang, const float* pos,
+                       float* y, float* stats, const uint64_t* rng, void* stream);
+int hamt_obj_embed_bwd(const hamt_obj_embed_desc* d, const hamt_obj_embed_params* p, const hamt_obj_embed_grads* g, const float* dy,
+                       const void* x1, const float* ang, const float* pos, const float* stats, float* dx, void* dx16, float* ws,
+                       const uint64_t* rng, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * ln: y = dropout_post( LayerNorm( dropout_pre(x) + residual ) )      fp32 statistics

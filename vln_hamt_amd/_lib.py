@@ -52,6 +52,24 @@ class VisEmbedDesc(C.Structure):
     _fields_ = [("M", i32), ("H", i32), ("A", i32), ("ld_ang", i32), ("eps1", f32), ("eps2", f32), ("x_bf16", i32), ("Mpad16", i32)]
 
 
+class ObjEmbedDesc(C.Structure):
+    _fields_ = [("M", i32), ("H", i32), ("A", i32), ("ld_ang", i32), ("P", i32), ("ld_pos", i32), ("eps_img", f32), ("eps_ang", f32),
+                ("eps_pos", f32), ("eps_out", f32), ("p_drop", f32), ("call_id", u32), ("x_bf16", i32), ("Mpad16", i32)]
+
+
+OBJ_EMBED_PARAMS = ("w_ang", "b_ang", "w_pos", "b_pos", "gamma_img", "beta_img", "gamma_ang", "beta_ang", "gamma_pos", "beta_pos",
+                    "tt", "nav", "gamma_out", "beta_out")
+
+
+class ObjEmbedParams(C.Structure):          # hamt_obj_embed_params: 14 device pointers
+    _fields_ = [(n, vp) for n in OBJ_EMBED_PARAMS]
+
+
+class ObjEmbedGrads(C.Structure):           # hamt_obj_embed_grads: 14 device pointers (NULL: skipped)
+    _fields_ = [(n, vp) for n in ("dw_ang", "db_ang", "dw_pos", "db_pos", "dgamma_img", "dbeta_img", "dgamma_ang", "dbeta_ang",
+                                  "dgamma_pos", "dbeta_pos", "dtt", "dnav", "dgamma_out", "dbeta_out")]
+
+
 # name -> argtypes (every entry point of include/hamt.h; tests/test_abi.py cross-checks against the header)
 WGRAD_TABLE_ENTRY = 112     # HAMT_WGRAD_TABLE_ENTRY
 
@@ -85,6 +103,8 @@ SIGNATURES = {
     "hamt_attn_varlen_cross_bwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_vis_embed_fwd": [C.POINTER(VisEmbedDesc)] + [vp] * 12,
     "hamt_vis_embed_bwd": [C.POINTER(VisEmbedDesc)] + [vp] * 18,
+    "hamt_obj_embed_fwd": [C.POINTER(ObjEmbedDesc), C.POINTER(ObjEmbedParams)] + [vp] * 7,
+    "hamt_obj_embed_bwd": [C.POINTER(ObjEmbedDesc), C.POINTER(ObjEmbedParams), C.POINTER(ObjEmbedGrads)] + [vp] * 10,
     "hamt_ln_fwd": [C.POINTER(LnDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_ln_bwd": [C.POINTER(LnDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_ln_bwd_add": [C.POINTER(LnDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
@@ -184,7 +204,7 @@ def workspace_bytes(op: int, *shape) -> int:
     return int(load().hamt_workspace_bytes(op, arr, len(shape)))
 
 
-WS_GEMM_SPLITK, WS_COLSUM, WS_SUMSQ, WS_LN_BWD, WS_WGRAD_TABLE, WS_LNRED_TABLE, WS_VIS_EMBED_BWD, WS_EMBED_BWD = range(8)
+WS_GEMM_SPLITK, WS_COLSUM, WS_SUMSQ, WS_LN_BWD, WS_WGRAD_TABLE, WS_LNRED_TABLE, WS_VIS_EMBED_BWD, WS_EMBED_BWD, WS_OBJ_EMBED_BWD = range(9)
 
 
 def check(rc: int, name: str):

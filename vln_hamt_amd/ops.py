@@ -770,6 +770,134 @@ def vis_embed(img, ang, img_lin, img_ln, ang_lin, ang_ln, prec, want16=False):
     return y
 
 
+# ------------------------------------------------------------------------------------------ REVERIE object embedding
+OBJ_EMBED = os.environ.get("HAMT_OBJ_EMBED", "1") == "1"
+# bf16 dense output in front of the fused kernel (bf16 mode): off by default, as HAMT_VIS_EMBED_X16
+OBJ_EMBED_X16 = os.environ.get("HAMT_OBJ_EMBED_X16", "0") == "1"
+_OE_GRAD_IN = (7, 8, 11, 12, 5, 6, 9, 10, 13, 14, 15, 16, 17, 18)   # hamt_obj_embed_grads field i <- ObjEmbedFn input _OE_GRAD_IN[i]
+_OE_ROW = {15: 1, 16: 2}                                              # token_type row 1, nav_type row 2 (the STOP type)
+
+
+def _rows_view(t: torch.Tensor, M: int, W: int) -> torch.Tensor:
+    """[..., W] fp32 -> [M, W] with unit inner stride (any row stride: the agent's angle slices of a wider feature tensor)"""
+    t2 = t.reshape(M, W) if t.dtype == torch.float32 else t.to(torch.float32).reshape(M, W)
+    return t2 if (t2.stride(-1) == 1 and (M <= 1 or t2.stride(0) >= W)) else t2.contiguous()
+
+
+class ObjEmbedFn(torch.autograd.Function):
+    """y = dropout(LN_out(LN_img(img_linear(obj)) + LN_ang(ang_linear(ang)) + LN_pos(pos_linear(pos)) + nav[2] + tt[1]))
+    (reverie/vlnbert_navref.py:31-42): the dense layer, then ONE launch for both small projections, the four LayerNorms, the two
+    constant rows and the dropout (hamt_obj_embed_fwd; csrc/obj_embed.hip); backward one launch + a deterministic reduction, the
+    image stream's gradient leaving as the bf16 image img_linear's queued weight gradient reads.  `tt` / `nav` are the whole
+    token-type / navigation-type tables: their rows 1 / 2 receive colsum(d(LN_out input)), ADDED to whatever else those rows get."""
+
+    @staticmethod
+    def forward(ctx, obj, ang, pos, w1, b1, g_img, be_img, w_ang, b_ang, g_ang, be_ang, w_pos, b_pos, g_pos, be_pos, tt, nav,
+                g_out, be_out, eps, p_drop, prec):
+        _chk(obj, "ObjEmbedFn")
+        K, H = obj.shape[-1], w1.shape[0]
+        x2 = obj.reshape(-1, K)
+        if x2.stride(-1) != 1:
+            x2 = x2.contiguous()
+        M = x2.shape[0]
+        dev = obj.device
+        a2, p2 = _rows_view(ang, M, ang.shape[-1]), _rows_view(pos, M, pos.shape[-1])
+        x16 = prep_x16(x2, prec)
+        x1 = torch.empty(M, H, dtype=torch.bfloat16 if (x16 is not None and OBJ_EMBED_X16) else torch.float32, device=dev)
+        _linear_fwd(x2, w1, b1.detach() if b1 is not None else None, x1, ACT_NONE, prec, None, x16)
+        y = torch.empty(M, H, dtype=torch.float32, device=dev)
+        stats = torch.empty(8, M, dtype=torch.float32, device=dev)
+        cid = next_call_id() if p_drop > 0 else 0
+        d = L.ObjEmbedDesc(M, H, a2.shape[1], a2.stride(0), p2.shape[1], p2.stride(0), *[float(e) for e in eps], float(p_drop), cid,
+                           int(x1.dtype == torch.bfloat16), 0)
+        params = (w_ang, b_ang, w_pos, b_pos, g_img, be_img, g_ang, be_ang, g_pos, be_pos, tt, nav, g_out, be_out)
+        pp = ObjEmbedFn._params(params, H)
+        L.check(L.load().hamt_obj_embed_fwd(C.byref(d), C.byref(pp), _p(x1), _p(a2), _p(p2), _p(y), _p(stats), _p(rng_state(dev)), _stream()),
+                "hamt_obj_embed_fwd")
+        ctx.save_for_backward(x2 if x16 is None else None, x16, x1, a2, p2, stats, w1, *params)
+        ctx.args = (tuple(float(e) for e in eps), float(p_drop), cid, prec, obj.shape, b1 is not None)
+        ctx.bias_param = b1 if (b1 is not None and b1.is_leaf) else (None if b1 is None else False)
+        ctx.grad_params = {i: p for i, p in zip(range(7, 19), (w_ang, b_ang, g_ang, be_ang, w_pos, b_pos, g_pos, be_pos, tt, nav, g_out, be_out))}
+        ctx.grad_params.update({5: g_img, 6: be_img})
+        ctx.set_materialize_grads(False)
+        return y.view(*obj.shape[:-1], H)
+
+    @staticmethod
+    def _params(params, H):
+        ptrs = []
+        for name, t in zip(L.OBJ_EMBED_PARAMS, params):
+            t = t.detach()
+            assert t.is_contiguous() and t.dtype == torch.float32, name
+            row = 1 if name == "tt" else (2 if name == "nav" else 0)
+            ptrs.append(t.data_ptr() + row * H * 4)
+        return L.ObjEmbedParams(*ptrs)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if dy is None:
+            return (None,) * 22
+        x2, x16, x1, a2, p2, stats, w1, *params = ctx.saved_tensors
+        eps, p_drop, cid, prec, oshape, has_b1 = ctx.args
+        M, H = x1.shape
+        dev = dy.device
+        dy2 = dy.reshape(M, H).contiguous()
+        from . import wgrad
+        in_pass = wgrad.ENABLED and torch._C._current_graph_task_id() >= 0
+        fast = x16 is not None
+        Mp = _rup(M) if fast else 0
+        dx16 = torch.empty(Mp, H, dtype=torch.bfloat16, device=dev) if fast else None
+        dx = None if fast else torch.empty(M, H, dtype=torch.float32, device=dev)
+        ptrs, rets = [], {}
+        for i in _OE_GRAD_IN:
+            if not ctx.needs_input_grad[i]:
+                ptrs.append(None)
+                continue
+            p = ctx.grad_params[i]
+            t, r = _grad_dst(p, p.shape, dev, in_pass)
+            if r is None:
+                wgrad.queue(dev).current()          # (opens the pass: orders this stream behind an overlapped optimizer update)
+            rets[i] = (p, t, r)
+            ptrs.append(t.data_ptr() + _OE_ROW.get(i, 0) * H * 4)
+        g = L.ObjEmbedGrads(*ptrs)
+        ws = torch.empty(L.workspace_bytes(L.WS_OBJ_EMBED_BWD, M, H) // 4, dtype=torch.float32, device=dev)
+        d = L.ObjEmbedDesc(M, H, a2.shape[1], a2.stride(0), p2.shape[1], p2.stride(0), *eps, p_drop, cid, int(x1.dtype == torch.bfloat16), Mp)
+        pp = ObjEmbedFn._params(params, H)
+        L.check(L.load().hamt_obj_embed_bwd(C.byref(d), C.byref(pp), C.byref(g), _p(dy2), _p(x1), _p(a2), _p(p2), _p(stats), _p(dx), _p(dx16),
+                                            _p(ws), _p(rng_state(dev)), _stream()), "hamt_obj_embed_bwd")
+        out = [None] * 22
+        for i, (p, t, r) in rets.items():
+            if r is None:
+                wgrad.publish_slot_grad(p, t)
+            out[i] = r
+        dobj, dw1, db1 = _linear_bwd(dx16[:M] if fast else dx, x2, x16, w1, prec, ctx.needs_input_grad[0], ctx.needs_input_grad[3],
+                                     has_b1 and ctx.needs_input_grad[4], dy16=dx16, bias_param=ctx.bias_param)
+        out[0] = dobj.view(oshape) if dobj is not None else None
+        out[3], out[4] = dw1, db1
+        return tuple(out)
+
+
+def obj_embed_ok(obj, ang, pos, emb, tt, nav) -> bool:
+    """the fused object embedder applies: fp32 features on the GPU, 4 angle / 5 position features, H % 64 == 0, H <= 1024, fp32
+    16-byte aligned parameters (`emb` = the ObjectEmbeddings module, tt / nav = the token-type / navigation-type tables)"""
+    H = emb.img_linear.weight.shape[0]
+    if not (OBJ_EMBED and obj.is_cuda and obj.dtype == torch.float32 and ang.shape[-1] == 4 and pos.shape[-1] == 5
+            and H % 64 == 0 and H <= 1024 and emb.ang_linear.bias is not None and emb.pos_linear.bias is not None):
+        return False
+    ts = [emb.ang_linear.weight, emb.ang_linear.bias, emb.pos_linear.weight, emb.pos_linear.bias, tt, nav]
+    ts += [m.weight for m in (emb.img_layer_norm, emb.ang_layer_norm, emb.pos_layer_norm, emb.layer_norm)]
+    ts += [m.bias for m in (emb.img_layer_norm, emb.ang_layer_norm, emb.pos_layer_norm, emb.layer_norm)]
+    return (emb.img_linear.weight.dtype == torch.float32 and tt.shape[0] > 1 and nav.shape[0] > 2
+            and all(t.dtype == torch.float32 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts))
+
+
+def obj_embed(obj, ang, pos, emb, tt, nav, p_drop, prec):
+    """ObjEmbedFn over the parameters of an ObjectEmbeddings module `emb` (reverie/vlnbert_navref.py)"""
+    il, al, pl = emb.img_linear, emb.ang_linear, emb.pos_linear
+    n1, n2, n3, n4 = emb.img_layer_norm, emb.ang_layer_norm, emb.pos_layer_norm, emb.layer_norm
+    return ObjEmbedFn.apply(obj, ang, pos, il.weight, il.bias, n1.weight, n1.bias, al.weight, al.bias, n2.weight, n2.bias, pl.weight, pl.bias,
+                            n3.weight, n3.bias, tt, nav, n4.weight, n4.bias, (n1.eps, n2.eps, n3.eps, n4.eps), float(p_drop), prec)
+
+
 # ------------------------------------------------------------------------------------------ gathers / embeddings
 class EmbedSumFn(torch.autograd.Function):
     """word[ids] + position[:L] + token_type[0]  (vilmodel.py:62-66; int64 gather is bit exact)."""
