@@ -65,10 +65,11 @@ int hamt_last_kernel(char* buf, size_t n);
  *   HAMT_WS_VIS_EMBED_BWD {M, H}    hamt_vis_embed_bwd `ws`
  *   HAMT_WS_EMBED_BWD     {R, H}    hamt_embed_sum_bwd `ws`
  *   HAMT_WS_OBJ_EMBED_BWD {M, H}    hamt_obj_embed_bwd `ws`
+ *   HAMT_WS_IMAGE_PREP    {n}       hamt_image_prep `ws`
  * returns the size in bytes, or 0 for an unknown op / malformed shape */
 enum { HAMT_WS_GEMM_SPLITK = 0, HAMT_WS_COLSUM = 1, HAMT_WS_SUMSQ = 2, HAMT_WS_LN_BWD = 3, HAMT_WS_WGRAD_TABLE = 4, HAMT_WS_LNRED_TABLE = 5, HAMT_WS_VIS_EMBED_BWD = 6,
        HAMT_WS_EMBED_BWD = 7 /* {R, H}: hamt_embed_sum_bwd `ws` = max(HAMT_WS_COLSUM {R, H}, 136 R bytes) */,
-       HAMT_WS_OBJ_EMBED_BWD = 8 };
+       HAMT_WS_OBJ_EMBED_BWD = 8, HAMT_WS_IMAGE_PREP = 9 /* {n}: hamt_image_prep `ws` */ };
 size_t hamt_workspace_bytes(int op, const int* shape, int nshape);
 
 /* ------------------------------------------------------------------------------------------------
@@ -411,6 +412,38 @@ int hamt_sum_rows(int B, int S, int H, const float* x, int mode, float* out, flo
 /* image [N][C][H][W] fp32 -> patch rows y[N*(H/P)*(W/P) .. Rpad)[C*P*P] (fp32 or bf16; rows beyond the patches zero): column
  * order = the flattened conv weight [D][C][P][P], so PatchEmbed's conv (vision_transformer.py:216-221) becomes one GEMM */
 int hamt_patchify(int N, int C, int H, int W, int P, const float* x, void* y, int ldy, int dtype_y, int Rpad, void* stream);
+/* Panorama view transform of the image-input pipeline (pretrain_src/data/image_data.py:70-80, 225-237: timm's create_transform,
+ * one PIL call chain per view on the host): for every OUTPUT slot i, crop box (left, top, width, height) of source view `src`
+ * (uint8 [H][W][3] as stored) -> PIL's BICUBIC resize of the crop to 224 x 224 -> horizontal flip -> colour jitter ->
+ * x / 255 -> (x - 0.5) / 0.5, PIL's / torch's result bit for bit (integer resampling taps, float32 blends rounded to uint8 after
+ * every op; see csrc/image_prep.hip).  `order`: the three jitter ops from first to last in bits [1:0], [3:2], [5:4], each one of
+ * HAMT_JIT_* (HAMT_JIT_SKIP: nothing), contrast at most once.  A slot with `zero` != 0
+ * or src < 0 is written as 0.0 (padded history steps, the killed observation: image_tasks.py:61-69, 181-183).
+ * Output: HAMT_IMAGE_NCHW fp32 y[n][3][224][224], or HAMT_IMAGE_PATCHES: the rows hamt_patchify(n, 3, 224, 224, 16, ...) makes of
+ * that tensor (ldy, dtype_y fp32 / bf16, Rpad; rows beyond n * 196 zero) -- the fp32 image is then never written.
+ * views_host / views_dev: the SAME table of n records in host memory (argument checks; read during the call only) and in device
+ * memory (read by the kernels).  lut: DEVICE, 256 floats, lut[u] = the normalised value of byte u (made by the caller with the
+ * framework's own arithmetic).  ws: HAMT_WS_IMAGE_PREP {n} bytes of device scratch, 16-byte aligned; its previous content is
+ * irrelevant.  Two launches whatever n is (one when every slot is zero).  A crop box outside the view, an empty box, a misaligned
+ * output, a short Rpad or ws: HAMT_ERR_ARG; a box side above 784 pixels: HAMT_ERR_UNSUPPORTED; nothing is launched then. */
+enum { HAMT_JIT_BRIGHTNESS = 0, HAMT_JIT_CONTRAST = 1, HAMT_JIT_SATURATION = 2, HAMT_JIT_SKIP = 3 };
+enum { HAMT_IMAGE_NCHW = 0, HAMT_IMAGE_PATCHES = 1 };
+typedef struct {
+  int32_t src;                       /* source view index in [0, n_src), < 0: none */
+  int32_t left, top, width, height;  /* crop box in pixels */
+  int32_t flip;
+  int32_t zero;
+  int32_t order;                     /* HAMT_JIT_* x 3 */
+  float brightness, contrast, saturation;
+  int32_t reserved;
+} hamt_image_view;                   /* 48 bytes */
+typedef struct {
+  int n, n_src, H, W;                /* output slots, source views, view size */
+  int layout;                        /* HAMT_IMAGE_* */
+  int ldy, dtype_y, Rpad;            /* HAMT_IMAGE_PATCHES only */
+} hamt_image_prep_desc;
+int hamt_image_prep(const hamt_image_prep_desc* d, const hamt_image_view* views_host, const hamt_image_view* views_dev,
+                    const uint8_t* src, const float* lut, void* y, void* ws, size_t ws_bytes, void* stream);
 int hamt_add3(size_t n, const float* a, const float* b, const float* c, float* out, void* stream);
 int hamt_dropout(size_t n, const float* x, float* y, float p, uint32_t call_id, const uint64_t* rng, void* stream);
 int hamt_cast_f32_bf16(size_t n, const float* x, void* y, void* stream);

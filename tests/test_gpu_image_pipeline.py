@@ -1,0 +1,380 @@
+"""GPU: the view-transform kernel (hamt_image_prep) against the numpy host path -- which tests/test_image_pipeline.py pins to PIL --
+bit for bit; the packed image batches of the six task collates against a host-built dict; the image-input model fed by them."""
+import ctypes as C
+import os
+import random
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from vln_hamt_amd import _lib as L
+from vln_hamt_amd.data import image_transform as T
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+TINY = os.path.join(GOLD, "r2r_tiny")
+DEV = "cuda:0"
+
+
+def _views(n, H, W, seed):
+    """alternating noise / smooth uint8 views"""
+    g = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = np.empty((n, H, W, 3), np.uint8)
+    for i in range(n):
+        if i % 2:
+            out[i] = g.integers(0, 256, (H, W, 3), dtype=np.uint8)
+        else:
+            out[i] = np.stack([127 + 120 * np.sin(xx / (5.0 + i + c) + yy / (9.0 + 2 * c) + i) for c in range(3)], -1).astype(np.uint8)
+    return out
+
+
+def _bits(a, b):
+    return torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+def _fixture():
+    from vln_hamt_amd.data.image_data import SyntheticPanoStore
+    z = np.load(os.path.join(GOLD, "image_prep.npz"))
+    recs = np.ascontiguousarray(z["recs"]).view(T.VIEW_DTYPE).reshape(-1)
+    store = SyntheticPanoStore(int(z["store_seed"]))
+    views = np.stack([store.get(str(k))[int(v)] for k, v in zip(z["keys"], z["view"])], 0)
+    return views, recs, z["out"]
+
+
+def test_kernel_equals_fixture_bitwise():
+    from vln_hamt_amd.data.image_prep import image_prep
+    views, recs, out = _fixture()
+    got = image_prep(torch.from_numpy(views).to(DEV), recs)
+    want = torch.from_numpy(T.normalize(out))
+    assert got.shape == (len(recs), 3, 224, 224) and _bits(got.cpu(), want)
+
+
+@pytest.mark.parametrize("H,W,n,seed", [(248, 330, 67, 1), (224, 224, 1, 2), (300, 260, 13, 3), (248, 330, 1, 4)])
+def test_kernel_equals_numpy_bitwise_random_draws(H, W, n, seed):
+    """train draws (boxes 0.08 .. 1 of the area: most of them upsample one side at least), eval, zero and src < 0 slots, slots
+    sharing a source view, n = 1 and n that no block size divides"""
+    from vln_hamt_amd.data.image_prep import image_prep
+    n_src = max(1, (n + 1) // 2)
+    views = _views(n_src, H, W, seed)
+    rng = random.Random(seed)
+    recs = np.zeros((n,), T.VIEW_DTYPE)
+    for i in range(n):
+        recs[i] = T.draw_train_params(rng, H, W)
+        recs[i]["src"] = rng.randrange(n_src)
+    if n > 8:
+        recs[3] = T.zero_record()
+        recs[5] = T.make_record(src=-1)
+        recs[6] = T.make_record((W - 31, H - 17, 31, 17), True, (1, 3, 3), (1.0, 1.37, 1.0))      # strong upsampling, contrast alone
+        recs[7] = T.make_record((0, 0, W, H), False, (3, 2, 3), (1.0, 1.0, 0.6))
+        if min(H, W) == 248:
+            recs[8] = T.draw_eval_params(H, W)
+        recs[9] = T.make_record((2, 1, 1, 1))                                                      # a single pixel
+    want = torch.from_numpy(T.transform_views(views, recs))
+    got = image_prep(torch.from_numpy(views).to(DEV), recs)
+    bad = (got.cpu() != want).flatten(1).sum(1)
+    assert int(bad.sum()) == 0, [(i, int(b), recs[i]) for i, b in enumerate(bad) if b][:4]
+    assert _bits(got.cpu(), want)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_patch_rows_equal_patchify(dtype):
+    from vln_hamt_amd.data.image_prep import image_prep
+    n, H, W = 5, 248, 330
+    views = _views(3, H, W, 11)
+    rng = random.Random(11)
+    recs = np.zeros((n,), T.VIEW_DTYPE)
+    for i in range(n):
+        recs[i] = T.draw_train_params(rng, H, W)
+        recs[i]["src"] = i % 3
+    recs[2] = T.zero_record()
+    src = torch.from_numpy(views).to(DEV)
+    x = image_prep(src, recs)
+    ldy, Rpad = 768 + 64, n * 196 + 60
+    code = L.HAMT_BF16 if dtype == torch.bfloat16 else L.HAMT_F32
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def filled():
+        t = torch.empty((Rpad, ldy), dtype=torch.float32 if dtype == torch.float32 else torch.int16, device=DEV)
+        t.view(torch.uint8).fill_(0xA5)
+        return t.view(dtype) if dtype == torch.bfloat16 else t
+    want = filled()
+    L.check(L.load().hamt_patchify(n, 3, 224, 224, 16, C.c_void_p(x.data_ptr()), C.c_void_p(want.data_ptr()), ldy, code, Rpad, st), "hamt_patchify")
+    got = image_prep(src, recs, layout="patches", out=filled(), ldy=ldy, Rpad=Rpad)
+    assert got.n == n and got.shape == (n, 3, 224, 224)
+    assert _bits(got.rows.cpu(), want.cpu())                 # columns beyond K keep the fill in both, rows beyond the patches are zero
+    assert float(got.rows[n * 196:, :768].float().abs().max()) == 0.0
+
+
+def test_two_runs_identical_and_scratch_content_irrelevant():
+    from vln_hamt_amd.data.image_prep import image_prep
+    n, H, W = 9, 248, 330
+    views = _views(4, H, W, 21)
+    rng = random.Random(21)
+    recs = np.zeros((n,), T.VIEW_DTYPE)
+    for i in range(n):
+        recs[i] = T.draw_train_params(rng, H, W)
+        recs[i]["src"] = i % 4
+    recs[4] = T.zero_record()
+    src = torch.from_numpy(views).to(DEV)
+    nbytes = L.workspace_bytes(L.WS_IMAGE_PREP, n)
+    assert nbytes >= n * 224 * 224 * 3
+    a = image_prep(src, recs)
+    b = image_prep(src, recs)
+    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=DEV)
+    c = image_prep(src, recs, ws=ws, out=torch.full((n, 3, 224, 224), float("nan"), device=DEV))
+    ws2 = torch.full((nbytes // 4,), float("nan"), device=DEV).view(torch.uint8)
+    d = image_prep(src, recs, ws=ws2)
+    assert _bits(a, b) and _bits(a, c) and _bits(a, d)
+    assert float(a[4].abs().max()) == 0.0
+
+
+def test_bad_arguments_launch_nothing():
+    from vln_hamt_amd.data.image_prep import image_prep
+    H, W = 248, 330
+    src = torch.from_numpy(_views(1, H, W, 5)).to(DEV)
+    lib = L.load()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ok = T.make_record((10, 10, 100, 100))
+    for bad in (T.make_record((300, 10, 100, 100)), T.make_record((10, 200, 100, 100)), T.make_record((-1, 0, 10, 10)),
+                T.make_record((10, 10, 0, 5)), T.make_record((10, 10, 5, 0)), T.make_record((0, 0, 10, 10), src=1),
+                T.make_record((0, 0, 10, 10), order=(1, 1, 3))):
+        recs = np.array([ok, bad], T.VIEW_DTYPE)
+        out = torch.full((2, 3, 224, 224), 7.0, device=DEV)
+        with pytest.raises(L.HamtError):
+            image_prep(src, recs, out=out)
+        torch.cuda.synchronize()
+        assert float((out - 7.0).abs().max()) == 0.0            # not even the valid slot was written
+    # misaligned output, short Rpad, short scratch: straight at the C entry point
+    recs = np.array([ok], T.VIEW_DTYPE)
+    rdev = torch.from_numpy(recs.view(np.uint8).copy()).to(DEV)
+    from vln_hamt_amd.data.image_prep import norm_table_on
+    lut = norm_table_on(torch.device(DEV))
+    ws = torch.empty(L.workspace_bytes(L.WS_IMAGE_PREP, 1), dtype=torch.uint8, device=DEV)
+    out = torch.full((3 * 224 * 224 + 4,), 7.0, device=DEV)
+
+    def call(desc, y, ws_bytes=ws.numel()):
+        return lib.hamt_image_prep(C.byref(desc), C.c_void_p(recs.ctypes.data), C.c_void_p(rdev.data_ptr()), C.c_void_p(src.data_ptr()),
+                                   C.c_void_p(lut.data_ptr()), C.c_void_p(y), C.c_void_p(ws.data_ptr()), ws_bytes, st)
+    assert call(L.ImagePrepDesc(1, 1, H, W, L.IMAGE_NCHW, 0, L.HAMT_F32, 0), out.data_ptr() + 4) == -1
+    assert call(L.ImagePrepDesc(1, 1, H, W, L.IMAGE_PATCHES, 768, L.HAMT_F32, 195), out.data_ptr()) == -1
+    assert call(L.ImagePrepDesc(1, 1, H, W, L.IMAGE_PATCHES, 766, L.HAMT_F32, 196), out.data_ptr()) == -1
+    assert call(L.ImagePrepDesc(1, 1, H, W, L.IMAGE_NCHW, 0, L.HAMT_F32, 0), out.data_ptr(), ws.numel() - 1) == -1
+    assert call(L.ImagePrepDesc(1, 1, H, W, 5, 0, L.HAMT_F32, 0), out.data_ptr()) == -1
+    torch.cuda.synchronize()
+    assert float((out - 7.0).abs().max()) == 0.0
+    assert "hamt_image_prep" in L.last_error()
+    assert call(L.ImagePrepDesc(1, 1, H, W, L.IMAGE_NCHW, 0, L.HAMT_F32, 0), out.data_ptr()) == 0
+
+
+# ------------------------------------------------------------------------------------------------ collates and model
+DIMS = dict(image_feat_size=16, image_prob_size=10, angle_feat_size=4)
+TOK = types.SimpleNamespace(cls_token_id=101, sep_token_id=102, mask_token_id=103, pad_token_id=0)
+STEP_TASKS = ("sap", "sar", "sprel")
+
+
+def _image_sets(hw=(64, 80), seed=77, **kw):
+    from vln_hamt_amd import data as D
+    args = dict(traj_files=[os.path.join(TINY, "traj.jsonl"), os.path.join(TINY, "traj2.jsonl")], img_ft_file=os.path.join(TINY, "img_fts.npz"),
+                scanvp_cands_file=os.path.join(TINY, "scanvp_cands.json"), connectivity_dir=TINY, max_txt_len=12, max_act_len=6, **DIMS)
+    args.update(kw)
+    db = D.MultiStepNavImageData(img_db=D.SyntheticPanoStore(1, height=hw[0], width=hw[1]), is_training=True, rng=random.Random(seed), **args)
+    return db, {"mlm": D.MlmImageDataset(db, TOK), "mrc": D.MrcImageDataset(db, TOK, 0.5), "itm": D.ItmImageDataset(db, TOK),
+                "sap": D.SapImageDataset(db, TOK, 0.3, 0.43), "sar": D.SarImageDataset(db, TOK, 0.3, 0.43),
+                "sprel": D.SprelImageDataset(db, TOK, 0.3, 0.43)}
+
+
+def _pad(rows, pad=0):
+    """data/common.py `pad_tensors` / pad_sequence: (B, max len, ...) filled with `pad`"""
+    rows = [torch.as_tensor(r) for r in rows]
+    n = max(r.shape[0] for r in rows)
+    out = torch.full((len(rows), n) + tuple(rows[0].shape[1:]), pad, dtype=rows[0].dtype)
+    for i, r in enumerate(rows):
+        out[i, :r.shape[0]] = r
+    return out
+
+
+def _host_collate(task, items):
+    """the dict of image_tasks.py's collates, built on the host: images through the numpy transform"""
+    B = len(items)
+    hist = [int(x["hist_lens"]) for x in items]
+    none = task in STEP_TASKS and max(hist) == 0
+    want = {"txt_ids": _pad([x["txt_ids"] for x in items]), "txt_lens": torch.tensor([x["txt_lens"] for x in items]),
+            "hist_lens": torch.tensor([h + 1 for h in hist])}
+    want["txt_masks"] = torch.arange(want["txt_ids"].shape[1])[None] < want["txt_lens"][:, None]
+    want["hist_masks"] = torch.arange(max(hist) + 1)[None] < want["hist_lens"][:, None]
+    if "txt_labels" in items[0]:
+        want["txt_labels"] = _pad([x["txt_labels"] for x in items], -1)
+
+    def images(key):
+        out = []
+        for x in items:
+            recs = np.atleast_1d(x[key])
+            views = np.concatenate(x["image_views"], 0) if x["image_views"] else np.zeros((0, 1, 1, 3), np.uint8)
+            out.append(torch.from_numpy(T.transform_views(views, recs.reshape(-1))).reshape(recs.shape + (3, 224, 224)))
+        return _pad(out)
+    for k in ("hist_ang_fts", "hist_pano_ang_fts"):
+        want[k] = None if none else _pad([x[k] for x in items])
+    for k in ("hist_images", "hist_pano_images"):
+        want[k] = None if none else images(k)
+    for k in ("hist_img_probs", "hist_mrc_masks"):
+        if k in items[0]:
+            want[k] = _pad([x[k] for x in items])
+    if "ob_images" in items[0]:
+        want["ob_images"] = images("ob_images")
+        want["ob_v_exists"] = torch.tensor([x["ob_v_exists"] for x in items])
+        want["ob_ang_fts"], want["ob_nav_types"] = _pad([x["ob_ang_fts"] for x in items]), _pad([x["ob_nav_types"] for x in items])
+        want["ob_lens"] = torch.tensor([x["ob_lens"] for x in items])
+        want["ob_masks"] = torch.arange(37)[None] < want["ob_lens"][:, None]
+    for k, dt in (("ob_action_viewindex", torch.int64), ("sp_anchor_idxs", torch.int64), ("ob_action_angles", torch.float32),
+                  ("ob_progress", torch.float32), ("sp_targets", torch.float32)):
+        if k in items[0]:
+            want[k] = torch.as_tensor(np.asarray([np.asarray(x[k]) for x in items])).to(dt)
+    return want
+
+
+def _same_batch(got, want):
+    assert set(want) <= set(got), set(want) - set(got)
+    assert "image_views" not in got and "hist_anages" not in got
+    for k, v in want.items():
+        if v is None:
+            assert got[k] is None, k
+        else:
+            g = got[k].cpu()
+            assert g.dtype == v.dtype and g.shape == v.shape, (k, g.dtype, v.dtype, g.shape, v.shape)
+            assert _bits(g, v), k
+
+
+@pytest.mark.parametrize("task", ["mlm", "mrc", "itm", "sap", "sar", "sprel"])
+def test_collate_to_device_equals_host_dict(task):
+    from vln_hamt_amd import data as D
+    _, sets = _image_sets()
+    random.seed(3); np.random.seed(3)
+    idx = (0, 4, 9) if task in STEP_TASKS else (0, 2)
+    items = [sets[task][i] for i in idx]
+    assert len({int(x["hist_lens"]) for x in items}) > 1                      # ragged: padded history slots exist
+    want = _host_collate(task, items)
+    pb = D.IMAGE_COLLATE[task](items).pin_memory()
+    assert isinstance(pb, D.PackedImageBatch)
+    got = pb.to_device(DEV)
+    _same_batch(got, want)
+    if want["hist_images"] is not None:
+        ref = (sets[task].nav_db.traj_step_refer if task in STEP_TASKS else sets[task].nav_db.traj_refer)
+        for b, i in enumerate(idx):
+            vidx = sets[task].nav_db.traj_data[ref[i][0]]["path_viewindex"]
+            for t in range(int(items[b]["hist_lens"])):
+                assert _bits(got["hist_images"][b, t], got["hist_pano_images"][b, t, vidx[t]])
+    # static tensors are filled in place
+    out = {k: torch.full_like(got[k], float("nan")) for k in ("hist_pano_images", "hist_images") if got[k] is not None}
+    out["txt_ids"] = torch.zeros_like(got["txt_ids"])
+    again = D.move_to_cuda(pb, DEV, out=out)
+    for k, t in out.items():
+        assert again[k] is t and _bits(t, got[k]), k
+    # the patch form of the same batch == hamt_patchify of the float form
+    pr = pb.to_device(DEV, image_layout="patches")
+    lib, st = L.load(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for k in ("hist_images", "hist_pano_images", "ob_images"):
+        if got.get(k) is None:
+            assert pr.get(k) is None
+            continue
+        x, p = got[k].reshape(-1, 3, 224, 224), pr[k]
+        assert isinstance(p, D.PatchRows) and p.shape == got[k].shape and p.rows.shape[0] % 64 == 0
+        y = torch.empty_like(p.rows)
+        L.check(lib.hamt_patchify(x.shape[0], 3, 224, 224, 16, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), 768, L.HAMT_F32, y.shape[0], st), "hamt_patchify")
+        assert _bits(p.rows, y), k
+
+
+def test_step_zero_batch_has_no_history():
+    from vln_hamt_amd import data as D
+    db, sets = _image_sets()
+    zero = [i for i, r in enumerate(db.traj_step_refer) if r[2] == 0][:2]
+    random.seed(4); np.random.seed(4)
+    items = [sets["sap"][i] for i in zero]
+    got = D.sap_image_collate(items).to_device(DEV)
+    _same_batch(got, _host_collate("sap", items))
+    assert got["hist_images"] is None and got["hist_pano_images"] is None and got["hist_ang_fts"] is None and got["hist_pano_ang_fts"] is None
+    assert got["ob_images"].shape == (2, 36, 3, 224, 224) and got["hist_masks"].shape == (2, 1)
+
+
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_model_on_loader_batches_patches_equals_nchw_equals_float(prec):
+    from _util import tiny_cfg
+    from oracle.hamt_oracle import make_state_dict, pretrain_param_shapes
+    from vln_hamt_amd import data as D
+    from vln_hamt_amd.model.image_pretrain import MultiStepNavImagePreTraining
+    from vln_hamt_amd.modeling import HamtConfig
+    ocfg = tiny_cfg(vocab_size=30522, image_prob_size=10)          # the tiny dataset's instructions are real bert-base word pieces
+    ocfg.image_feat_size = 128
+    for k in ("hidden_dropout_prob", "attention_probs_dropout_prob", "pred_head_dropout_prob"):
+        setattr(ocfg, k, 0.0)
+    torch.manual_seed(0)
+    model = MultiStepNavImagePreTraining(HamtConfig(hamt_precision=prec, **dict(vars(ocfg))), vit_kwargs=dict(depth=1, num_heads=2, mlp_ratio=2.0))
+    model.load_state_dict(make_state_dict(pretrain_param_shapes(ocfg), seed=3), strict=False)
+    model = model.to(DEV).train()
+    _, sets = _image_sets(max_txt_len=20)
+    for task, idx in (("sap", (4, 9)), ("mrc", (0, 2))):
+        random.seed(3); np.random.seed(3)
+        items = [sets[task][i] for i in idx]
+        pb = D.IMAGE_COLLATE[task](items).pin_memory()
+        host = _host_collate(task, items)
+
+        def run(batch):
+            model.zero_grad(set_to_none=True)
+            loss = model(batch, task, True)
+            loss.mean().backward()
+            torch.cuda.synchronize()
+            return loss.detach().clone(), {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
+        nchw = pb.to_device(DEV, image_layout="nchw")
+        flt = dict(nchw)
+        for k in ("hist_images", "hist_pano_images", "ob_images"):
+            if k in host:
+                flt[k] = host[k].to(DEV)
+        l0, g0 = run(flt)
+        l1, g1 = run(nchw)
+        l2, g2 = run(pb.to_device(DEV, image_layout="patches"))
+        assert torch.isfinite(l0).all() and any(n.startswith("bert.vision_backbone.patch_embed") for n in g0)
+        for l, g in ((l1, g1), (l2, g2)):
+            assert _bits(l0, l), task
+            assert set(g) == set(g0)
+            for n in g0:
+                assert _bits(g0[n], g[n]), (task, n)
+
+
+def test_loader_to_rangerlars_step():
+    from _util import tiny_cfg
+    from oracle.hamt_oracle import make_state_dict, pretrain_param_shapes
+    from vln_hamt_amd import data as D
+    from vln_hamt_amd.model.image_pretrain import MultiStepNavImagePreTraining
+    from vln_hamt_amd.modeling import HamtConfig
+    from vln_hamt_amd.optim.misc import build_optimizer
+    ocfg = tiny_cfg(vocab_size=30522, image_prob_size=10)          # the tiny dataset's instructions are real bert-base word pieces
+    ocfg.image_feat_size = 128
+    torch.manual_seed(0)
+    model = MultiStepNavImagePreTraining(HamtConfig(hamt_precision="bf16", **dict(vars(ocfg))), vit_kwargs=dict(depth=1, num_heads=2, mlp_ratio=2.0))
+    model.load_state_dict(make_state_dict(pretrain_param_shapes(ocfg), seed=3), strict=False)
+    model = model.to(DEV).train()
+    _, sets = _image_sets(max_txt_len=20)
+    opts = types.SimpleNamespace(train_batch_size=2, val_batch_size=2, local_rank=-1, n_workers=0, pin_mem=True, optim="rangerlars",
+                                 learning_rate=1e-3, betas=(0.9, 0.98), weight_decay=0.01)
+    opt = build_optimizer(model, opts)
+    for layout in ("patches", "nchw"):
+        loader, _ = D.build_dataloader("sap", sets["sap"], D.sap_image_collate, True, opts)
+        pre = D.PrefetchLoader(loader, torch.device(DEV), image_layout=layout)
+        batch = next(iter(pre))
+        assert isinstance(batch["ob_images"], D.PatchRows if layout == "patches" else torch.Tensor)
+        before = {n: p.detach().clone() for n, p in model.named_parameters()}
+        loss = model(batch, "sap", True).mean()
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+        torch.cuda.synchronize()
+        assert np.isfinite(float(loss))
+        assert all(torch.isfinite(p).all() for p in model.parameters())
+        assert any(not torch.equal(before[n], p) for n, p in model.named_parameters() if "vision_backbone" in n)
+        for st_ in opt.state.values():
+            for v in st_.values():
+                if torch.is_tensor(v):
+                    assert torch.isfinite(v).all()

@@ -70,6 +70,19 @@ class ObjEmbedGrads(C.Structure):           # hamt_obj_embed_grads: 14 device po
                                   "dgamma_pos", "dbeta_pos", "dtt", "dnav", "dgamma_out", "dbeta_out")]
 
 
+JIT_BRIGHTNESS, JIT_CONTRAST, JIT_SATURATION, JIT_SKIP = 0, 1, 2, 3     # HAMT_JIT_*
+IMAGE_NCHW, IMAGE_PATCHES = 0, 1                                        # HAMT_IMAGE_*
+
+
+class ImageView(C.Structure):               # hamt_image_view (48 bytes; data.image_transform.VIEW_DTYPE is its numpy mirror)
+    _fields_ = [("src", C.c_int32), ("left", C.c_int32), ("top", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("flip", C.c_int32),
+                ("zero", C.c_int32), ("order", C.c_int32), ("brightness", f32), ("contrast", f32), ("saturation", f32), ("reserved", C.c_int32)]
+
+
+class ImagePrepDesc(C.Structure):
+    _fields_ = [("n", i32), ("n_src", i32), ("H", i32), ("W", i32), ("layout", i32), ("ldy", i32), ("dtype_y", i32), ("Rpad", i32)]
+
+
 # name -> argtypes (every entry point of include/hamt.h; tests/test_abi.py cross-checks against the header)
 WGRAD_TABLE_ENTRY = 112     # HAMT_WGRAD_TABLE_ENTRY
 
@@ -122,6 +135,7 @@ SIGNATURES = {
     "hamt_mul_bcast_bwd": [i32, i32, i32, vp, vp, i32, vp, vp, vp, vp],
     "hamt_sum_rows": [i32, i32, i32, vp, i32, vp, vp, vp],
     "hamt_patchify": [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp],
+    "hamt_image_prep": [C.POINTER(ImagePrepDesc), vp, vp, vp, vp, vp, vp, sz, vp],
     "hamt_add3": [sz, vp, vp, vp, vp, vp],
     "hamt_dropout": [sz, vp, vp, f32, u32, vp, vp],
     "hamt_cast_f32_bf16": [sz, vp, vp, vp],
@@ -205,6 +219,7 @@ def workspace_bytes(op: int, *shape) -> int:
 
 
 WS_GEMM_SPLITK, WS_COLSUM, WS_SUMSQ, WS_LN_BWD, WS_WGRAD_TABLE, WS_LNRED_TABLE, WS_VIS_EMBED_BWD, WS_EMBED_BWD, WS_OBJ_EMBED_BWD = range(9)
+WS_IMAGE_PREP = 9
 
 
 def check(rc: int, name: str):

@@ -40,6 +40,7 @@ extern "C" int hamt_last_kernel(char* buf, size_t n) {
 extern "C" int hamt_gemm_ksplit(const hamt_gemm_desc* d);
 size_t hamt_vis_embed_ws_bytes(int M, int H);   // vis_embed.hip
 size_t hamt_obj_embed_ws_bytes(int M, int H);   // obj_embed.hip
+size_t hamt_image_prep_ws_bytes(int n);         // image_prep.hip
 
 extern "C" size_t hamt_workspace_bytes(int op, const int* shape, int nshape) {
   switch (op) {
@@ -63,6 +64,7 @@ extern "C" size_t hamt_workspace_bytes(int op, const int* shape, int nshape) {
     case HAMT_WS_LNRED_TABLE: return nshape >= 1 && shape ? (size_t)shape[0] * HAMT_LNRED_TABLE_ENTRY : 0;
     case HAMT_WS_VIS_EMBED_BWD: return nshape >= 2 && shape ? hamt_vis_embed_ws_bytes(shape[0], shape[1]) : 0;
     case HAMT_WS_OBJ_EMBED_BWD: return nshape >= 2 && shape ? hamt_obj_embed_ws_bytes(shape[0], shape[1]) : 0;
+    case HAMT_WS_IMAGE_PREP: return nshape >= 1 && shape ? hamt_image_prep_ws_bytes(shape[0]) : 0;
     case HAMT_WS_EMBED_BWD: {
       if (nshape < 2 || !shape) return 0;
       const size_t a = (size_t)64 * shape[1] * 4, b = (size_t)136 * shape[0];

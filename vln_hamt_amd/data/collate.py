@@ -27,7 +27,8 @@ RAGGED = {"txt_ids": ("txt", 0x00), "txt_labels": ("txt", 0xFF),
           "hist_img_probs": ("hist", 0), "hist_mrc_masks": ("hist", 0),
           "ob_img_fts": ("ob", 0), "ob_ang_fts": ("ob", 0), "ob_nav_types": ("ob", 0)}
 PER_SAMPLE = {"ob_action_viewindex": torch.int64, "sp_anchor_idxs": torch.int64, "ob_action_angles": torch.float32,
-              "ob_progress": torch.float32, "sp_targets": torch.float32}
+              "ob_progress": torch.float32, "sp_targets": torch.float32,
+              "ob_v_exists": torch.bool}          # image-input tasks only (image_tasks.py:184)
 HIST_FIELDS = ("hist_img_fts", "hist_ang_fts", "hist_pano_img_fts", "hist_pano_ang_fts")
 _ALIGN = 64
 
@@ -54,7 +55,12 @@ class PackedBatch:
     def nbytes(self) -> int:
         return self.buf.numel()
 
-    def to_device(self, device, out: Optional[Dict[str, torch.Tensor]] = None, text_pack: bool = False) -> Dict[str, object]:
+    def _unpack_extra(self, dbuf, device, res, out, **extra):
+        """hook of subclasses that carry more than the ragged fields (data/image_tasks.py); runs on the current stream"""
+        if extra:
+            raise TypeError(f"{type(self).__name__}.to_device: unexpected arguments {sorted(extra)}")
+
+    def to_device(self, device, out: Optional[Dict[str, torch.Tensor]] = None, text_pack: bool = False, **extra) -> Dict[str, object]:
         """H2D copy of the buffer + unpack kernels on the current stream -> the reference's collated batch on `device`.
         `out`: tensors to fill in place where key, shape and dtype match (static inputs of a captured graph).
         `text_pack`: add the text packing plan of the batch (`txt_pack_idx`, `txt_cu`, `txt_unpack_idx`: synth.text_pack_plan over the
@@ -114,13 +120,15 @@ class PackedBatch:
             if plan is not None:
                 for name, t in zip(("txt_pack_idx", "txt_cu", "txt_unpack_idx"), plan):
                     res[name] = t.pin_memory().to(device, non_blocking=True)
+        self._unpack_extra(dbuf, device, res, out, **extra)
         dbuf.record_stream(torch.cuda.current_stream(device))
         return res
 
 
-def _pack(task: str, inputs: List[dict]) -> PackedBatch:
+def _pack(task: str, inputs: List[dict], skip=(), tail_bytes: int = 0, cls=None) -> PackedBatch:
+    """`skip`: keys left to the caller; `tail_bytes`: room kept at the end of the buffer (from `.tail_off`) for them; `cls`: the batch type"""
     B = len(inputs)
-    keys = list(inputs[0].keys())
+    keys = [k for k in inputs[0].keys() if k not in skip]
     fams = {"txt": [int(x["txt_lens"]) for x in inputs], "hist": [int(x["hist_lens"]) for x in inputs]}
     if "ob_lens" in keys:
         fams["ob"] = [int(x["ob_lens"]) for x in inputs]
@@ -146,7 +154,8 @@ def _pack(task: str, inputs: List[dict]) -> PackedBatch:
             off = _rup(off + int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=PER_SAMPLE[k]).element_size())
         elif k not in ("txt_lens", "hist_lens", "ob_lens"):
             lists[k] = [x[k] for x in inputs]
-    buf = torch.empty(max(off, _ALIGN), dtype=torch.uint8)
+    tail_off = off
+    buf = torch.empty(max(off + tail_bytes, _ALIGN), dtype=torch.uint8)
     # ---- fill: one copy per sample and field, no padding, no zero fill of the payload
     for fam, lens in fams.items():
         pre = np.zeros(B + 1, dtype=np.int32)
@@ -166,7 +175,9 @@ def _pack(task: str, inputs: List[dict]) -> PackedBatch:
         esz = torch.empty((), dtype=dtype).element_size()
         vals = torch.as_tensor(np.asarray([np.asarray(x[k]) for x in inputs])).to(dtype)
         buf[o:o + vals.numel() * esz].view(dtype).view(shape).copy_(vals)
-    return PackedBatch(task, B, buf, fields, per_sample, fams, prefix_off, lists, hist_none)
+    pb = (cls or PackedBatch)(task, B, buf, fields, per_sample, fams, prefix_off, lists, hist_none)
+    pb.tail_off = tail_off
+    return pb
 
 
 def mlm_collate(inputs):

@@ -1,0 +1,247 @@
+"""The per-view image transform of the image-input pipeline on the host, in numpy, and its random parameter draws.
+
+The reference runs timm's `create_transform((3, 224, 224), mean = std = 0.5, interpolation="bicubic", crop_pct=0.9, is_training=...)`
+on every uint8 view (pretrain_src/data/image_data.py:70-80, 225-237).  With timm's defaults (no auto-augment, re_prob 0) that is
+
+    train:  RandomResizedCrop(scale (0.08, 1), ratio (3/4, 4/3), bicubic) -> RandomHorizontalFlip(0.5) -> ColorJitter(0.4, 0.4, 0.4)
+            (brightness, contrast, saturation factors U(0.6, 1.4) in a random order; hue off) -> ToTensor -> Normalize(0.5, 0.5)
+    eval:   Resize(248) (a no-op on a view whose short side is 248) -> CenterCrop(224) -> ToTensor -> Normalize(0.5, 0.5)
+
+Here a draw is a small RECORD (`VIEW_DTYPE`, the numpy mirror of `hamt_image_view` in include/hamt.h) and the transform a pure function
+of (uint8 view, record): `apply_view` is the CPU path of the pipeline, `hamt_image_prep` (csrc/image_prep.hip) the GPU path, and both
+reproduce PIL bit for bit (tests/test_image_pipeline.py chains PIL == numpy == fixture, tests/test_gpu_image_pipeline.py numpy ==
+kernel).  The arithmetic is therefore PIL's, integer where PIL's is:
+
+* resize = `Image.crop(box).resize((224, 224), Image.BICUBIC)`: two passes of 8-bit resampling over the cropped image (Resample.c:
+  tap weights in double, normalised, 22-bit fixed point, `clip8((2^21 + sum k p) >> 22)`, horizontal first);
+* jitter = `ImageEnhance.{Brightness, Contrast, Color}` = `Image.blend(degenerate, image, factor)` in float32, truncated -- clipped
+  when the factor is outside [0, 1] -- and rounded to uint8 after every op; contrast's degenerate is `int(mean(grey) + 0.5)` of the
+  image as it is when the op runs, grey = `(19595 R + 38470 G + 7471 B + 0x8000) >> 16`;
+* normalisation = `torch.from_numpy(u8).float().div(255).sub(0.5).div(0.5)` through a 256-entry table made with exactly that.
+
+The random STREAM of the draws is this module's own: timm / torchvision draw from python's and torch's global generators in an order
+that cannot be replayed without them, so only the distributions (supports, probabilities) are restated, not the sequence.
+"""
+from __future__ import annotations
+
+import math
+import random
+from typing import Sequence
+
+import numpy as np
+
+IMGSIZE = 224
+HEIGHT, WIDTH = 248, 330                        # the reference's stored view size (image_data.py:20-22)
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_SKIP = 0, 1, 2, 3        # HAMT_JIT_*
+ORDERS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+NO_JITTER = OP_SKIP | OP_SKIP << 2 | OP_SKIP << 4
+
+VIEW_DTYPE = np.dtype([("src", "<i4"), ("left", "<i4"), ("top", "<i4"), ("width", "<i4"), ("height", "<i4"), ("flip", "<i4"),
+                       ("zero", "<i4"), ("order", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"),
+                       ("reserved", "<i4")])
+assert VIEW_DTYPE.itemsize == 48
+
+
+def pack_order(ops: Sequence[int]) -> int:
+    return int(ops[0]) | int(ops[1]) << 2 | int(ops[2]) << 4
+
+
+def unpack_order(order: int):
+    return (order & 3, (order >> 2) & 3, (order >> 4) & 3)
+
+
+def make_record(box=(0, 0, IMGSIZE, IMGSIZE), flip=False, order=NO_JITTER, factors=(1.0, 1.0, 1.0), src=0, zero=False):
+    """one VIEW_DTYPE record; `box` = (left, top, width, height), `factors` = (brightness, contrast, saturation)"""
+    r = np.zeros((), VIEW_DTYPE)
+    r["src"], r["left"], r["top"], r["width"], r["height"] = src, box[0], box[1], box[2], box[3]
+    r["flip"], r["zero"], r["order"] = int(bool(flip)), int(bool(zero)), order if isinstance(order, (int, np.integer)) else pack_order(order)
+    r["brightness"], r["contrast"], r["saturation"] = factors
+    return r
+
+
+def zero_record():
+    """a slot that is written as all 0.0 (padded history steps, the killed observation)"""
+    return make_record(src=-1, zero=True)
+
+
+# ------------------------------------------------------------------------------------------------ parameter draws
+def _uniform(rng, a, b):
+    return float(rng.uniform(a, b))
+
+
+def _randint(rng, lo, hi):
+    """integer in [lo, hi], both ends included"""
+    if isinstance(rng, random.Random):
+        return rng.randint(lo, hi)
+    return int(rng.integers(lo, hi + 1))
+
+
+def draw_eval_params(H=HEIGHT, W=WIDTH):
+    """timm's eval transform at crop_pct 0.9: Resize(int(224 / 0.9) = 248) + CenterCrop(224).  The resize is the identity on a view
+    whose short side is 248 -- the only case a (crop, 1:1 resize) record can express, so anything else is an error."""
+    if min(H, W) != int(math.floor(IMGSIZE / 0.9)):
+        raise ValueError(f"eval transform: the short side of a {H} x {W} view is not {int(math.floor(IMGSIZE / 0.9))}; Resize(248) "
+                         "would resample the whole view, which a crop record cannot express")
+    return make_record(box=(int(round((W - IMGSIZE) / 2.0)), int(round((H - IMGSIZE) / 2.0)), IMGSIZE, IMGSIZE))
+
+
+def draw_box(rng, H, W, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """RandomResizedCrop.get_params -> ((left, top, width, height), fell_back)"""
+    area = H * W
+    for _ in range(10):
+        target = _uniform(rng, *scale) * area
+        aspect = math.exp(_uniform(rng, math.log(ratio[0]), math.log(ratio[1])))
+        w = int(round(math.sqrt(target * aspect)))
+        h = int(round(math.sqrt(target / aspect)))
+        if 0 < w <= W and 0 < h <= H:
+            top = _randint(rng, 0, H - h)
+            left = _randint(rng, 0, W - w)
+            return (left, top, w, h), False
+    in_ratio = W / H                                       # fallback: centre crop, ratio clamped
+    if in_ratio < min(ratio):
+        w = W
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = H
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = W, H
+    return ((W - w) // 2, (H - h) // 2, w, h), True
+
+
+def draw_train_params(rng, H=HEIGHT, W=WIDTH, jitter=0.4, hflip=0.5):
+    """one independent training draw (`rng`: random.Random or numpy Generator): box, flip, three factors, their order"""
+    box, _ = draw_box(rng, H, W)
+    flip = _uniform(rng, 0.0, 1.0) < hflip
+    factors = tuple(_uniform(rng, 1.0 - jitter, 1.0 + jitter) for _ in range(3))
+    order = ORDERS[_randint(rng, 0, 5)]
+    return make_record(box=box, flip=flip, order=order, factors=factors)
+
+
+# ------------------------------------------------------------------------------------------------ resize
+def _cubic(x):
+    x = np.abs(x)
+    return np.where(x < 1.0, ((1.5 * x - 2.5) * x) * x + 1.0, np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5, 0.0))
+
+
+_TAPS: dict = {}
+
+
+def resample_taps(in_size: int, out_size: int = IMGSIZE):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc (BICUBIC) -> (xmin [out], count [out], k [out, ksize] int32, zero beyond count)"""
+    key = (in_size, out_size)
+    if key in _TAPS:
+        return _TAPS[key]
+    scale = np.float64(in_size) / np.float64(out_size)
+    fs = max(scale, np.float64(1.0))
+    support, ss = 2.0 * fs, 1.0 / fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
+    cnt = xmax - xmin
+    w = np.zeros((out_size, ksize), np.float64)
+    ww = np.zeros(out_size, np.float64)
+    for x in range(ksize):                                  # sequential sum, as the C loop
+        wx = np.where(x < cnt, _cubic((x + xmin - center + 0.5) * ss), 0.0)
+        w[:, x] = wx
+        ww = ww + wx
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    k = np.where(w < 0.0, np.trunc(-0.5 + w * 4194304.0), np.trunc(0.5 + w * 4194304.0)).astype(np.int32)
+    k[np.arange(ksize)[None, :] >= cnt[:, None]] = 0
+    if len(_TAPS) > 4096:
+        _TAPS.clear()
+    _TAPS[key] = (xmin, cnt, k)
+    return _TAPS[key]
+
+
+def _pass(img, in_size, axis):
+    """one 8-bit resampling pass along `axis` (0: rows, 1: columns) of a uint8 (h, w, 3) image"""
+    xmin, cnt, k = resample_taps(in_size)
+    idx = np.minimum(xmin[:, None] + np.arange(k.shape[1])[None, :], in_size - 1)        # taps beyond `count` have weight 0
+    acc = np.full((IMGSIZE, img.shape[1], 3) if axis == 0 else (img.shape[0], IMGSIZE, 3), 1 << 21, np.int32)
+    src = img.astype(np.int32)
+    for t in range(k.shape[1]):
+        if axis == 0:
+            acc += src[idx[:, t]] * k[:, t][:, None, None]
+        else:
+            acc += src[:, idx[:, t]] * k[:, t][None, :, None]
+    return np.clip(acc >> 22, 0, 255).astype(np.uint8)
+
+
+def resize_bicubic_u8(crop: np.ndarray) -> np.ndarray:
+    """uint8 (h, w, 3) -> uint8 (224, 224, 3) == Image.fromarray(crop).resize((224, 224), Image.BICUBIC)"""
+    h, w = crop.shape[:2]
+    return _pass(_pass(crop, w, 1), h, 0)
+
+
+# ------------------------------------------------------------------------------------------------ colour jitter
+def grey(img: np.ndarray) -> np.ndarray:
+    v = img.astype(np.int32)
+    return (19595 * v[..., 0] + 38470 * v[..., 1] + 7471 * v[..., 2] + 0x8000) >> 16
+
+
+def blend(deg, img: np.ndarray, factor) -> np.ndarray:
+    """Image.blend(degenerate, image, factor) on uint8 data"""
+    f = np.float32(factor)
+    d = np.asarray(deg).astype(np.float32)
+    t = d + f * (img.astype(np.float32) - d)
+    if 0.0 <= f <= 1.0:
+        return t.astype(np.int32).astype(np.uint8)
+    return np.where(t <= 0.0, 0, np.where(t >= 255.0, 255, t.astype(np.int32))).astype(np.uint8)
+
+
+def jitter_op(img: np.ndarray, op: int, factor) -> np.ndarray:
+    if op == OP_BRIGHTNESS:
+        return blend(0, img, factor)
+    if op == OP_CONTRAST:
+        g = grey(img)
+        return blend((2 * int(g.sum()) + g.size) // (2 * g.size), img, factor)           # int(mean + 0.5)
+    if op == OP_SATURATION:
+        return blend(grey(img)[..., None], img, factor)
+    return img
+
+
+# ------------------------------------------------------------------------------------------------ the transform
+def apply_view(view: np.ndarray, rec) -> np.ndarray:
+    """uint8 (H, W, 3) view + record -> the transformed uint8 (224, 224, 3) image BEFORE normalisation"""
+    left, top, w, h = int(rec["left"]), int(rec["top"]), int(rec["width"]), int(rec["height"])
+    H, W = view.shape[:2]
+    if w < 1 or h < 1 or left < 0 or top < 0 or left + w > W or top + h > H:
+        raise ValueError(f"crop box ({left}, {top}, {w}, {h}) outside the {H} x {W} view")
+    img = resize_bicubic_u8(np.asarray(view[top:top + h, left:left + w]))
+    if int(rec["flip"]):
+        img = img[:, ::-1]
+    factors = (rec["brightness"], rec["contrast"], rec["saturation"])
+    for op in unpack_order(int(rec["order"])):
+        if op != OP_SKIP:
+            img = jitter_op(img, op, factors[op])
+    return np.ascontiguousarray(img)
+
+
+_LUT = None
+
+
+def norm_table():
+    """float32 [256]: byte -> normalised value, with torch's own arithmetic"""
+    global _LUT
+    if _LUT is None:
+        import torch
+        _LUT = torch.arange(256, dtype=torch.uint8).float().div(255).sub(0.5).div(0.5).numpy()
+    return _LUT
+
+
+def normalize(img_u8: np.ndarray) -> np.ndarray:
+    """uint8 (..., 224, 224, 3) -> float32 (..., 3, 224, 224)"""
+    return np.ascontiguousarray(np.moveaxis(norm_table()[img_u8], -1, -3))
+
+
+def transform_views(views: np.ndarray, recs: np.ndarray) -> np.ndarray:
+    """views uint8 (n_src, H, W, 3), recs VIEW_DTYPE [n] -> float32 (n, 3, 224, 224): the tensor the reference's batch keys hold
+    (slots with `zero` or src < 0 are 0.0)"""
+    recs = np.atleast_1d(recs)
+    out = np.zeros((len(recs), 3, IMGSIZE, IMGSIZE), np.float32)
+    for i, r in enumerate(recs):
+        if not int(r["zero"]) and int(r["src"]) >= 0:
+            out[i] = normalize(apply_view(views[int(r["src"])], r))
+    return out

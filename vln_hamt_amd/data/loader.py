@@ -83,23 +83,25 @@ class MetaLoader:
             yield task, batch
 
 
-def move_to_cuda(batch, device, out=None, text_pack=False):
-    """loader.py:77-87, plus PackedBatch -> the collated dict on `device` (text_pack: see PackedBatch.to_device)"""
+def move_to_cuda(batch, device, out=None, text_pack=False, image_layout=None):
+    """loader.py:77-87, plus PackedBatch -> the collated dict on `device` (text_pack: see PackedBatch.to_device; image_layout: "nchw" /
+    "patches" for the batches of data/image_tasks.py, None = their default)"""
     if isinstance(batch, PackedBatch):
-        return batch.to_device(device, out=out, text_pack=text_pack)
+        kw = {} if image_layout is None else {"image_layout": image_layout}
+        return batch.to_device(device, out=out, text_pack=text_pack, **kw)
     if isinstance(batch, torch.Tensor):
         return batch.to(device, non_blocking=True)
     if isinstance(batch, list):
-        return [move_to_cuda(t, device, text_pack=text_pack) for t in batch]
+        return [move_to_cuda(t, device, text_pack=text_pack, image_layout=image_layout) for t in batch]
     if isinstance(batch, tuple):
-        return tuple(move_to_cuda(t, device, text_pack=text_pack) for t in batch)
+        return tuple(move_to_cuda(t, device, text_pack=text_pack, image_layout=image_layout) for t in batch)
     if isinstance(batch, dict):
-        return {n: move_to_cuda(t, device, text_pack=text_pack) for n, t in batch.items()}
+        return {n: move_to_cuda(t, device, text_pack=text_pack, image_layout=image_layout) for n, t in batch.items()}
     return batch
 
 
 def _record(obj, stream):
-    if isinstance(obj, torch.Tensor):
+    if isinstance(obj, torch.Tensor) or hasattr(obj, "record_stream"):       # (PatchRows: data/image_prep.py)
         obj.record_stream(stream)
     elif isinstance(obj, (list, tuple)):
         for t in obj:
@@ -113,10 +115,12 @@ class PrefetchLoader:
     """overlap compute and host->device transfer (loader.py:90-124): same `__iter__` / `__len__` / attribute forwarding;
     the transfer of batch i+1 is issued on a copy stream as soon as batch i has been handed out."""
 
-    def __init__(self, loader, device: torch.device, text_pack: bool = False):
-        """text_pack: batches carry their text packing plan (three index tensors beyond the reference's keys, PackedBatch.to_device)"""
+    def __init__(self, loader, device: torch.device, text_pack: bool = False, image_layout=None):
+        """text_pack: batches carry their text packing plan (three index tensors beyond the reference's keys, PackedBatch.to_device);
+        image_layout: form of the prepared views of image-input batches ("nchw" / "patches", data/image_tasks.py)"""
         self.loader = loader
         self.text_pack = text_pack
+        self.image_layout = image_layout
         self.device = torch.device(device)
         # (one HIP stream per role and process, distinct from the capture / side / update / exchange streams: streams.role_stream)
         self.stream = None
@@ -142,10 +146,10 @@ class PrefetchLoader:
             self.batch = None
             return
         if self.stream is None:
-            self.batch = move_to_cuda(self.batch, self.device, text_pack=self.text_pack)
+            self.batch = move_to_cuda(self.batch, self.device, text_pack=self.text_pack, image_layout=self.image_layout)
             return
         with torch.cuda.stream(self.stream):
-            self.batch = move_to_cuda(self.batch, self.device, text_pack=self.text_pack)
+            self.batch = move_to_cuda(self.batch, self.device, text_pack=self.text_pack, image_layout=self.image_layout)
 
     def next(self, it):
         batch = self.batch

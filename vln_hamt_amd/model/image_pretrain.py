@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import torch
 
+from ..data.image_prep import PatchRows
 from .pretrain_cmt import MultiStepNavCMTPreTraining
 from .vision_transformer import VisionTransformer
 
@@ -29,10 +30,11 @@ class MultiStepNavImagePreTraining(MultiStepNavCMTPreTraining):
         self.bert.vision_backbone = VisionTransformer(**kw)
 
     def forward_vision_backbone(self, images, detach=False):
-        """image_vilmodel.py:40-59"""
+        """image_vilmodel.py:40-59.  `images`: a float tensor, or the `PatchRows` form of one (data/image_prep.py: the patch rows of
+        the flattened views, as the loader's `image_layout="patches"` delivers them)"""
         is_pano = images.dim() == 6
         lead = images.shape[:3] if is_pano else images.shape[:2]
-        flat = images.reshape(-1, *images.shape[-3:])
+        flat = images if isinstance(images, PatchRows) else images.reshape(-1, *images.shape[-3:])
         if is_pano:
             with torch.no_grad():
                 feats = self.bert.vision_backbone.forward_features(flat)
@@ -57,6 +59,8 @@ class MultiStepNavImagePreTraining(MultiStepNavCMTPreTraining):
             of = self.forward_vision_backbone(fb["ob_images"])
             ex = fb.get("ob_v_exists")
             if ex is not None:                                                              # :101-102
-                of = of.masked_fill(ex.logical_not().unsqueeze(-1), 0)
+                if ex.dim() == 1:                    # [N] as the reference's collates give it (image_tasks.py:215); [N, V] also taken
+                    ex = ex.unsqueeze(-1)
+                of =of.masked_fill(ex.logical_not().unsqueeze(-1), 0)
             fb["ob_img_fts"] = torch.cat([of, of.new_zeros(of.shape[0], 1, of.shape[2])], 1)   # STOP token (:104-106)
         return super().forward(fb, task, compute_loss)

@@ -28,6 +28,7 @@ from torch import nn
 
 from .. import _lib as L
 from .. import blocks_preln, ops, streams
+from ..data.image_prep import PatchRows
 from ..ops import _p, _stream
 
 
@@ -117,6 +118,15 @@ class PatchEmbed(nn.Module):
     def forward(self, x):
         if not x.is_cuda:
             raise L.HamtError("PatchEmbed: input must live on the GPU (no CPU fallback)")
+        if isinstance(x, PatchRows):                # the image-prep kernel already wrote the rows hamt_patchify would make
+            P = self.patch_size[0]
+            rows, K = x.n * self.num_patches, 3 * P * P
+            assert self.img_size == (224, 224) and P == 16 and x.rows.shape[0] >= rows and x.rows.shape[1] >= K, "PatchRows are 224 x 224 views in 16 x 16 patches"
+            patches = x.rows[:rows, :K]
+            if patches.dtype != torch.float32 or not patches.is_contiguous():
+                patches = patches.float().contiguous()
+            y = ops.linear(patches, self.proj.weight.view(self.proj.weight.shape[0], K), self.proj.bias, ops.ACT_NONE, self.prec)
+            return y.view(x.n, self.num_patches, -1)
         B, Cc, H, W = x.shape
         assert (H, W) == self.img_size, f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
         P = self.patch_size[0]
@@ -147,6 +157,7 @@ class VisionTransformer(nn.Module):
         nn.init.trunc_normal_(self.cls_token, std=0.02)
 
     def forward_features(self, x):
+        """x: float images (B, 3, H, W), or a `PatchRows` holder (data/image_prep.py) standing for such a tensor"""
         streams.gate(self.cls_token, self.pos_embed, self.norm)                      # (called as a method: no module hook in front)
         x = self.patch_embed(x)                                                      # (B, N, D)
         B, N, D = x.shape
