@@ -4,8 +4,9 @@
     python vln_hamt_amd/csrc/build.py [--force]
 
 Objects go to csrc/build/, the library next to the Python package (vln_hamt_amd/libhamt_hip.so), so it
-travels with the tree to the GPU box.  Re-compiles only sources newer than their object.
+travels with the tree to the GPU box.  Re-compiles only sources whose object is older than the source or than any header.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -28,7 +29,7 @@ def hipcc():
 
 def build(force=False, verbose=True):
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
-    deps = [os.path.join(HERE, "common.h"), os.path.join(HERE, "gemm_frag.h"), os.path.join(HERE, "gemm_epi.h"), os.path.join(HERE, "gemm_args.h"), os.path.join(ROOT, "include", "hamt.h")]
+    deps = glob.glob(os.path.join(HERE, "*.h")) + [os.path.join(ROOT, "include", "hamt.h")]    # any header rebuilds every source
     dep_m = max(os.path.getmtime(d) for d in deps)
     jobs = []
     for s in SOURCES:

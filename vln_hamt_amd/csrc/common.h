@@ -101,6 +101,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ void wave_sum2(float& a, float& b) {      // two / three sums in one pass: the shuffles interleave
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+}
+__device__ __forceinline__ void wave_sum3(float& a, float& b, float& c) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -140,3 +148,6 @@ __device__ __forceinline__ void g8_unpack4(uint32_t w, float* o) {
 }
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// out[N] (+)= sum over r < R of ws[r][N], rows added in order (gemm.hip)
+void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s);

@@ -6,8 +6,6 @@
 // fusion products (pretrain_cmt.py:176, vilmodel.py:722) and the -inf fill (pretrain_cmt.py:177).
 #include "common.h"
 
-void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s);
-
 namespace {
 
 __global__ void gather_rows_kernel(int R, int W, const float* __restrict__ src, int ld_src,

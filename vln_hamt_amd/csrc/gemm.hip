@@ -15,8 +15,6 @@
 // 182, 263, 284, 323-325, 497-498, 549-558; pretrain_cmt.py:16-68).
 #include "common.h"
 
-void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s);
-
 namespace {
 
 struct GemmArgs {

@@ -29,7 +29,6 @@
 #include <type_traits>
 #include <vector>
 
-void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s);
 bool hamt_gemm_q4_launch(const GemmArgsF& g, bool b_kmajor, hipStream_t s);      // gemm_q4.hip: the 128-square tile with a four-deep operand ring
 
 

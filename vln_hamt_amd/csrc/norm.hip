@@ -1,24 +1,21 @@
 // LayerNorm family for gfx950:  y = dropout_post( LN( dropout_pre(x) + residual ) ), fp32 statistics.
-// One 64-lane wave per row (H <= 1024 kept in registers as float4s), 4 rows per 256-thread block,
-// wave-shuffle reductions, 16-byte coalesced loads/stores.  HBM/L2-bound: 3 reads + 2 writes per element.
+// One 64-lane wave per row, the row in registers, 4 rows per 256-thread block: the row layout, its I/O and arithmetic and the
+// column-sum reduction are ln_row.h's.  HBM/L2-bound: 3 reads + 2 writes per element.
 //
 // Replaces BertSelfOutput/BertOutput's dropout+add+LayerNorm (vilmodel.py:139-143, 181-185), the
 // LayerNorm+dropout tails of BertEmbeddings / ImageEmbeddings / HistoryEmbeddings (vilmodel.py:67-68,
 // 503-504, 545-546, 570-571) and the LN(+Dropout) inside the prediction heads (pretrain_cmt.py:18-19).
-#include "common.h"
-
-void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s);
+#include "ln_row.h"
 
 namespace {
 
-// keep factors of the 4 consecutive elements (row, c .. c+3), c % 4 == 0: the 4-wide mask stream of common.h (one hash
-// pair per 4 elements instead of two hashes per element -- the LayerNorm-backward kernel spent 15 % of its time hashing)
-__device__ __forceinline__ void ln_keep4(RngKey k, int row, int c, float p, float inv_keep, float (&f)[4]) {
-  drop_scale4(k, hamt_mix32((uint32_t)row ^ k.k0), (uint32_t)(c >> 2), p, inv_keep, f);
-}
-
-
 constexpr uint32_t POST_SALT = 0x5bd1e995u;
+
+// io16: the dense layer in front wrote x as fp32, bf16 (what autocast does with a linear's output) or IEEE half (HAMT_F16); the
+// saved sum z likewise, one bit higher
+static_assert(HAMT_LN_X_BF16 == LN_BF16 && HAMT_LN_X_F16 == LN_F16 && HAMT_LN_Z_BF16 == 2 * LN_BF16 && HAMT_LN_Z_F16 == 2 * LN_F16, "io16 layout");
+__device__ __forceinline__ int ln_xfmt(int io16) { return io16 & (LN_BF16 | LN_F16); }
+__device__ __forceinline__ int ln_zfmt(int io16) { return (io16 >> 1) & (LN_BF16 | LN_F16); }
 
 template <int NV>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(hamt_ln_desc d, const void* __restrict__ xv,
@@ -30,13 +27,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(hamt_ln_desc d, const void*
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + w;
   const int H = d.H;
-  if (row >= d.M) {   // rows [M, Mpad16) of the bf16 image are zero (they are reduction padding for the fast GEMMs)
-    if (y16 && row < d.Mpad16)
-      for (int c = lane * 4; c < H; c += 256) *(uint2*)(y16 + (size_t)row * H + c) = make_uint2(0u, 0u);
+  if (row >= d.M) {
+    if (y16) zero_pad_rows(y16, H, row, d.Mpad16, gridDim.x * 4, lane);
     return;
   }
   const RngKey kpre = rng_key(rng, d.call_id), kpost = rng_key(rng, d.call_id ^ POST_SALT);
   const float ik_pre = d.p_pre > 0.f ? 1.0f / (1.0f - d.p_pre) : 1.0f, ik_post = d.p_post > 0.f ? 1.0f / (1.0f - d.p_post) : 1.0f;
+  const int xfmt = ln_xfmt(d.io16);
   float4 v[NV];
   float sum = 0.f;
 #pragma unroll
@@ -44,33 +41,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(hamt_ln_desc d, const void*
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
       const size_t o = (size_t)row * H + c;
-      float4 a;
-      if (d.io16 & HAMT_LN_X_F16) {       // the dense layer in front wrote IEEE half (HAMT_F16)
-        const uint2 u = *(const uint2*)((const bf16_t*)xv + o);
-        unpack_h2(u.x, a.x, a.y); unpack_h2(u.y, a.z, a.w);
-      } else if (d.io16 & HAMT_LN_X_BF16) {      // the dense layer in front wrote bf16 (what autocast does with a linear's output)
-        const uint2 u = *(const uint2*)((const bf16_t*)xv + o);
-        a = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-      } else a = *(const float4*)((const float*)xv + o);
-      if (d.p_pre > 0.f) {
-        float f_[4]; ln_keep4(kpre, row, c, d.p_pre, ik_pre, f_);
-        a.x *= f_[0]; a.y *= f_[1]; a.z *= f_[2]; a.w *= f_[3];
-      }
-      if (res) { float4 r = *(const float4*)(res + o); a.x += r.x; a.y += r.y; a.z += r.z; a.w += r.w; }
+      float4 a = load_row4(xv, o, xfmt);
+      if (d.p_pre > 0.f) a = mul4(a, keep4(kpre, row, c, d.p_pre, ik_pre));
+      if (res) acc4(a, *(const float4*)(res + o));
       v[i] = a;
-      sum += a.x + a.y + a.z + a.w;
-    } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      sum += sum4(a);
+    } else v[i] = zero4();
   }
   const float mean = wave_sum(sum) / (float)H;
   float sq = 0.f;
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int c = (i * 64 + lane) * 4;
-    if (c < H) {
-      float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, e = v[i].w - mean;
-      sq += a * a + b * b + cc * cc + e * e;
-    }
-  }
+  for (int i = 0; i < NV; ++i)
+    if ((i * 64 + lane) * 4 < H) sq += sqdev4(v[i], mean);
   const float rstd = rsqrtf(wave_sum(sq) / (float)H + d.eps);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -79,19 +61,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(hamt_ln_desc d, const void*
       const size_t o = (size_t)row * H + c;
       if (zv) {
         if (d.io16 & HAMT_LN_Z_F16) *(uint2*)((bf16_t*)zv + o) = make_uint2(pack_h2(v[i].x, v[i].y), pack_h2(v[i].z, v[i].w));
-        else if (d.io16 & HAMT_LN_Z_BF16) *(uint2*)((bf16_t*)zv + o) = make_uint2(pack_bf2(v[i].x, v[i].y), pack_bf2(v[i].z, v[i].w));
+        else if (d.io16 & HAMT_LN_Z_BF16) store_bf4((bf16_t*)zv, o, v[i]);
         else *(float4*)((float*)zv + o) = v[i];
       }
-      const float4 g = *(const float4*)(gamma + c), b = *(const float4*)(beta + c);
-      float4 r;
-      r.x = (v[i].x - mean) * rstd * g.x + b.x; r.y = (v[i].y - mean) * rstd * g.y + b.y;
-      r.z = (v[i].z - mean) * rstd * g.z + b.z; r.w = (v[i].w - mean) * rstd * g.w + b.w;
-      if (d.p_post > 0.f) {
-        float f_[4]; ln_keep4(kpost, row, c, d.p_post, ik_post, f_);
-        r.x *= f_[0]; r.y *= f_[1]; r.z *= f_[2]; r.w *= f_[3];
-      }
+      float4 r = affine4(norm4(v[i], mean, rstd), *(const float4*)(gamma + c), *(const float4*)(beta + c));
+      if (d.p_post > 0.f) r = mul4(r, keep4(kpost, row, c, d.p_post, ik_post));
       if (y) *(float4*)(y + o) = r;
-      if (y16) *(uint2*)(y16 + o) = make_uint2(pack_bf2(r.x, r.y), pack_bf2(r.z, r.w));
+      if (y16) store_bf4(y16, o, r);
     }
   }
   if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
@@ -106,19 +82,16 @@ __global__ __launch_bounds__(64 * NWV) void ln_bwd_kernel(hamt_ln_desc d, const 
                                                      const float* __restrict__ add) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int H = d.H;
-  if (dx16 && blockIdx.x == 0)      // zero the reduction-padding rows [M, Mpad16) of the bf16 gradient image
-    for (int row = d.M + w; row < d.Mpad16; row += NWV)
-      for (int c = lane * 4; c < H; c += 256) *(uint2*)(dx16 + (size_t)row * H + c) = make_uint2(0u, 0u);
+  if (dx16 && blockIdx.x == 0) zero_pad_rows(dx16, H, d.M + w, d.Mpad16, NWV, lane);
   const RngKey kpre = rng_key(rng, d.call_id), kpost = rng_key(rng, d.call_id ^ POST_SALT);
   const float ik_pre = d.p_pre > 0.f ? 1.0f / (1.0f - d.p_pre) : 1.0f, ik_post = d.p_post > 0.f ? 1.0f / (1.0f - d.p_post) : 1.0f;
+  const int zfmt = ln_zfmt(d.io16);
   float4 gam[NV], dg[NV], db[NV], dxs[NV];   // dxs: column sums of dx = bias gradient of the dense layer that produced x
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 4;
-    gam[i] = c < H ? *(const float4*)(gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    dg[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    db[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    dxs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    gam[i] = c < H ? *(const float4*)(gamma + c) : zero4();
+    dg[i] = zero4(); db[i] = zero4(); dxs[i] = zero4();
   }
   for (int row = blockIdx.x * NWV + w; row < d.M; row += gridDim.x * NWV) {
     const float mean = mean_i[row], rstd = rstd_i[row];
@@ -130,23 +103,13 @@ __global__ __launch_bounds__(64 * NWV) void ln_bwd_kernel(hamt_ln_desc d, const 
       if (c < H) {
         const size_t o = (size_t)row * H + c;
         float4 a = *(const float4*)(dy + o);
-        if (d.p_post > 0.f) {
-          float f_[4]; ln_keep4(kpost, row, c, d.p_post, ik_post, f_);
-          a.x *= f_[0]; a.y *= f_[1]; a.z *= f_[2]; a.w *= f_[3];
-        }
-        float4 zz;
-        if (d.io16 & HAMT_LN_Z_F16) {
-          const uint2 u = *(const uint2*)((const bf16_t*)zv + o);
-          unpack_h2(u.x, zz.x, zz.y); unpack_h2(u.y, zz.z, zz.w);
-        } else if (d.io16 & HAMT_LN_Z_BF16) {
-          const uint2 u = *(const uint2*)((const bf16_t*)zv + o);
-          zz = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-        } else zz = *(const float4*)((const float*)zv + o);
-        float4 h;
-        h.x = (zz.x - mean) * rstd; h.y = (zz.y - mean) * rstd; h.z = (zz.z - mean) * rstd; h.w = (zz.w - mean) * rstd;
-        dg[i].x += a.x * h.x; dg[i].y += a.y * h.y; dg[i].z += a.z * h.z; dg[i].w += a.w * h.w;
-        db[i].x += a.x; db[i].y += a.y; db[i].z += a.z; db[i].w += a.w;
-        a.x *= gam[i].x; a.y *= gam[i].y; a.z *= gam[i].z; a.w *= gam[i].w;
+        if (d.p_post > 0.f) a = mul4(a, keep4(kpost, row, c, d.p_post, ik_post));
+        const float4 h = norm4(load_row4(zv, o, zfmt), mean, rstd);
+        fmacc4(dg[i], a, h);
+        acc4(db[i], a);
+        a = mul4(a, gam[i]);
+        // (spelled out, not sum4 / dot4: at NV = 1 the compiler pairs s1 with s2, and which products of s2 it contracts into FMAs
+        // follows the operand order of these two sums -- through the helpers 6 of its 36 FMAs became multiply + add)
         s1 += a.x + a.y + a.z + a.w;
         s2 += a.x * h.x + a.y * h.y + a.z * h.z + a.w * h.w;
         g[i] = a; xh[i] = h;
@@ -158,26 +121,23 @@ __global__ __launch_bounds__(64 * NWV) void ln_bwd_kernel(hamt_ln_desc d, const 
       const int c = (i * 64 + lane) * 4;
       if (c < H) {
         const size_t o = (size_t)row * H + c;
-        float4 r;
-        r.x = rstd * (g[i].x - c1 - xh[i].x * c2); r.y = rstd * (g[i].y - c1 - xh[i].y * c2);
-        r.z = rstd * (g[i].z - c1 - xh[i].z * c2); r.w = rstd * (g[i].w - c1 - xh[i].w * c2);
+        float4 r = ln_dx4(g[i], xh[i], c1, c2, rstd);
         if (add) {   // pre-LN block: the residual path's gradient rides along (dz_out = LN-backward + add); dx / dx16 /
           const float4 q = *(const float4*)(add + o);     // dxsum below stay the pure LayerNorm-input gradient
           *(float4*)(dz + o) = make_float4(r.x + q.x, r.y + q.y, r.z + q.z, r.w + q.w);
         } else *(float4*)(dz + o) = r;
-        if (d.p_pre > 0.f) {
-          float f_[4]; ln_keep4(kpre, row, c, d.p_pre, ik_pre, f_);
-          r.x *= f_[0]; r.y *= f_[1]; r.z *= f_[2]; r.w *= f_[3];
-        }
+        if (d.p_pre > 0.f) r = mul4(r, keep4(kpre, row, c, d.p_pre, ik_pre));
         if (dx) *(float4*)(dx + o) = r;
-        if (dx16) *(uint2*)(dx16 + o) = make_uint2(pack_bf2(r.x, r.y), pack_bf2(r.z, r.w));
-        dxs[i].x += r.x; dxs[i].y += r.y; dxs[i].z += r.z; dxs[i].w += r.w;
+        if (dx16) store_bf4(dx16, o, r);
+        acc4(dxs[i], r);
       }
     }
   }
   // block partials: ws[block][0][H] = dgamma, ws[block][1][H] = dbeta, ws[block][2][H] = sum dx
   // (NWV waves per block keep enough rows in flight to cover the HBM latency -- 4 waves per CU ran at 2.1 TB/s -- while the
-  // number of partials, one per block, stays <= 256: first a tree over the upper waves, then the 4-wave stage)
+  // number of partials, one per block, stays <= 256: first a tree over the upper waves, then the 4-wave stage in which waves
+  // 0..2 finish one vector each.  A measured design, see ln_bwd_geometry: not ln_row.h's block_partial, which sums one vector at a
+  // time over all waves in another order.)
   __shared__ float4 red[NWV > 4 ? NWV / 2 : 4][3][NV * 64];
 #pragma unroll
   for (int half = NWV / 2; half >= 4; half >>= 1) {
@@ -190,9 +150,7 @@ __global__ __launch_bounds__(64 * NWV) void ln_bwd_kernel(hamt_ln_desc d, const 
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         const float4 a = red[w][0][i * 64 + lane], b = red[w][1][i * 64 + lane], c = red[w][2][i * 64 + lane];
-        dg[i].x += a.x; dg[i].y += a.y; dg[i].z += a.z; dg[i].w += a.w;
-        db[i].x += b.x; db[i].y += b.y; db[i].z += b.z; db[i].w += b.w;
-        dxs[i].x += c.x; dxs[i].y += c.y; dxs[i].z += c.z; dxs[i].w += c.w;
+        acc4(dg[i], a); acc4(db[i], b); acc4(dxs[i], c);
       }
     }
     __syncthreads();
@@ -214,7 +172,7 @@ __global__ __launch_bounds__(64 * NWV) void ln_bwd_kernel(hamt_ln_desc d, const 
   }
 }
 
-// ws[block][3][H] -> dgamma[H], dbeta[H], dxsum[H] (each accumulated).  block = 64 columns x 16 partial-row phases.
+// ws[block][3][H] -> dgamma[H], dbeta[H], dxsum[H] (each overwritten).  block = 64 columns x 16 partial-row phases.
 __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(int nb, int H, const float* __restrict__ ws, float* __restrict__ dgamma,
                                                              float* __restrict__ dbeta, float* __restrict__ dxsum) {
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
@@ -236,36 +194,20 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(int nb, int H, cons
   }
 }
 
-// Same reduction for H % 64 == 0 with 16-byte loads: block = 64 columns (16 lanes x float4) x 16 phases; every thread keeps
-// its 16 (nb = 256) loads in flight before the first add.
+// Same reduction for H % 64 == 0 with 16-byte loads (ln_row.h's reduce_partials): block `blk` owns columns blk * 64 .. + 63 of
+// the 3 * H; every thread keeps its 16 (nb = 256) loads in flight before the first add.
+__device__ __forceinline__ bool ln_reduce4(int blk, int nb, int H, const float* __restrict__ ws, int& which, int& col, float4& t) {
+  const int c = blk * 64 + (threadIdx.x & 15) * 4;     // < 3 * H by construction
+  which = c / H; col = c - which * H;
+  return reduce_partials(ws + (size_t)which * H + col, (size_t)3 * H, nb, t);
+}
 __global__ __launch_bounds__(256) void ln_bwd_reduce4_kernel(int nb, int H, const float* __restrict__ ws, float* __restrict__ dgamma,
                                                              float* __restrict__ dbeta, float* __restrict__ dxsum) {
-  const int l16 = threadIdx.x & 15, ph = threadIdx.x >> 4;
-  const int c = blockIdx.x * 64 + l16 * 4;            // < 3 * H by construction
-  const int which = c / H, col = c - which * H;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b0 = ph; b0 < nb; b0 += 64) {              // 4 independent loads per trip
-    float4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int b = b0 + 16 * u;
-      v[u] = b < nb ? *(const float4*)(ws + ((size_t)b * 3 + which) * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-  }
-  __shared__ float4 red[16][16];
-  red[ph][l16] = s;
-  __syncthreads();
-  if (ph == 0) {
-    float* o = which == 0 ? dgamma : (which == 1 ? dbeta : dxsum);
-    if (o) {
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { const float4 r = red[i][l16]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
-      *(float4*)(o + col) = t;
-    }
-  }
+  int which, col;
+  float4 t;
+  if (!ln_reduce4(blockIdx.x, nb, H, ws, which, col, t)) return;
+  float* o = which == 0 ? dgamma : (which == 1 ? dbeta : dxsum);
+  if (o) *(float4*)(o + col) = t;
 }
 
 // Grouped form of the reduction: entry e owns blocks [e * bpe, (e + 1) * bpe) (bpe = 3 * Hmax / 64; blocks beyond an entry's
@@ -280,36 +222,15 @@ __global__ void ln_red_table_write_kernel(LnRedChunk c, LnRedEntry* tab, int off
 __global__ __launch_bounds__(256) void ln_bwd_reduce_grouped_kernel(const LnRedEntry* __restrict__ tab, int bpe) {
   const LnRedEntry q = tab[blockIdx.x / bpe];
   const int blk = blockIdx.x % bpe;
-  const int H = q.H, nb = q.nb;
-  if (blk * 64 >= 3 * H) return;
-  const int l16 = threadIdx.x & 15, ph = threadIdx.x >> 4;
-  const int c = blk * 64 + l16 * 4;
-  const int which = c / H, col = c - which * H;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b0 = ph; b0 < nb; b0 += 64) {
-    float4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int b = b0 + 16 * u;
-      v[u] = b < nb ? *(const float4*)(q.ws + ((size_t)b * 3 + which) * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-  }
-  __shared__ float4 red[16][16];
-  red[ph][l16] = s;
-  __syncthreads();
-  if (ph == 0) {
-    float* o = which == 0 ? q.dgamma : (which == 1 ? q.dbeta : q.dxsum);
-    if (o) {
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { const float4 r = red[i][l16]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
-      if ((q.atomic >> which) & 1) {     // the output is a gradient-arena slot shared with other uses of the parameter (zero at the start of a step)
-        atomicAdd(o + col, t.x); atomicAdd(o + col + 1, t.y); atomicAdd(o + col + 2, t.z); atomicAdd(o + col + 3, t.w);
-      } else *(float4*)(o + col) = t;
-    }
-  }
+  if (blk * 64 >= 3 * q.H) return;
+  int which, col;
+  float4 t;
+  if (!ln_reduce4(blk, q.nb, q.H, q.ws, which, col, t)) return;
+  float* o = which == 0 ? q.dgamma : (which == 1 ? q.dbeta : q.dxsum);
+  if (!o) return;
+  if ((q.atomic >> which) & 1) {     // the output is a gradient-arena slot shared with other uses of the parameter (zero at the start of a step)
+    atomicAdd(o + col, t.x); atomicAdd(o + col + 1, t.y); atomicAdd(o + col + 2, t.z); atomicAdd(o + col + 3, t.w);
+  } else *(float4*)(o + col) = t;
 }
 
 }  // namespace
@@ -323,12 +244,11 @@ extern "C" int hamt_ln_fwd(const hamt_ln_desc* d, const void* x, const float* re
   HAMT_CHECK_ARG((d->io16 & (HAMT_LN_X_BF16 | HAMT_LN_X_F16)) != (HAMT_LN_X_BF16 | HAMT_LN_X_F16) && (d->io16 & (HAMT_LN_Z_BF16 | HAMT_LN_Z_F16)) != (HAMT_LN_Z_BF16 | HAMT_LN_Z_F16),
                  "hamt_ln_fwd: io16 = %d names two formats for one tensor", d->io16);
   if (d->M == 0) return HAMT_OK;
-  const int nv = (d->H + 255) / 256;
   const int rows = (y16 && d->Mpad16 > d->M) ? d->Mpad16 : d->M;
   dim3 grid((rows + 3) / 4), block(256);
   hipStream_t s = as_stream(stream);
 #define LAUNCH(NV) hipLaunchKernelGGL((ln_fwd_kernel<NV>), grid, block, 0, s, *d, x, residual, gamma, beta, z, y, (bf16_t*)y16, mean, rstd, rng)
-  switch (nv) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+  LN_ROW_DISPATCH(d->H, LAUNCH)
 #undef LAUNCH
   HAMT_CHECK_LAUNCH("hamt_ln_fwd");
   return HAMT_OK;
@@ -360,14 +280,13 @@ static int ln_bwd_impl(const hamt_ln_desc* d, const float* dy, const void* z, co
   HAMT_CHECK_ARG(d->H % 4 == 0 && d->H >= 4 && d->H <= 1024, "hamt_ln_bwd: H=%d unsupported", d->H);
   HAMT_CHECK_ARG(!(d->p_pre > 0.f) || dx || dx16, "hamt_ln_bwd: p_pre > 0 needs dx or dx16");
   if (d->M == 0) return HAMT_OK;
-  const int nv = (d->H + 255) / 256;
   int nwv, nb;
   ln_bwd_geometry(d->M, &nwv, &nb);
   hipStream_t s = as_stream(stream);
   float* dxx = d->p_pre > 0.f ? dx : nullptr;
 #define LAUNCH2(NV, W) hipLaunchKernelGGL((ln_bwd_kernel<NV, W>), dim3(nb), dim3(64 * W), 0, s, *d, dy, z, mean, rstd, gamma, dz, dxx, (bf16_t*)dx16, ws, rng, add)
 #define LAUNCH(NV) { if (nwv == 16) LAUNCH2(NV, 16); else if (nwv == 8) LAUNCH2(NV, 8); else LAUNCH2(NV, 4); }
-  switch (nv) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+  LN_ROW_DISPATCH(d->H, LAUNCH)
 #undef LAUNCH
 #undef LAUNCH2
   if (dgamma || dbeta || dxsum) ln_bwd_reduce_launch(nb, d->H, ws, dgamma, dbeta, dxsum, s);

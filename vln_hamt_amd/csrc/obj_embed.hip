@@ -9,41 +9,22 @@
 // gradients; the 17 column sums (every gamma / beta, both projections' weights and biases, colsum(de) for the two constant rows)
 // leave as per-block partials that the second kernel sums in a fixed order into the gradient destinations.
 //
-// One 64-lane wave per row, H <= 1024 kept in registers as float4s.  All three branch LayerNorms may see a constant row (REVERIE
-// pads a viewpoint without objects with one all-zero row, and the fresh obj_embeddings have zero biases): the variance is then 0
-// and rstd = eps^-1/2 = 1e6, the normalised row 0 -- the output is beta, as in the reference, and no value is non-finite.
-#include "common.h"
+// One 64-lane wave per row; the row layout, its arithmetic, the K = 4 projection and the column-sum reduction are ln_row.h's (this
+// file multiplies its row sums by 1 / H where norm.hip and vis_embed.hip divide by H).  All three branch LayerNorms may see a
+// constant row (REVERIE pads a viewpoint without objects with one all-zero row, and the fresh obj_embeddings have zero biases):
+// the variance is then 0 and rstd = eps^-1/2 = 1e6, the normalised row 0 -- the output is beta, as in the reference, and no
+// value is non-finite.
+#include "ln_row.h"
 
 namespace {
 
-constexpr int OE_A = 4;            // angle features
+constexpr int OE_A = LN_ANGLE_K;   // angle features
 constexpr int OE_P = 5;            // position box features
 // per-block partial vectors: dgamma_out, dbeta_out, colsum(de), dgamma_img / ang / pos, db_ang, dW_ang[:, 0..3], db_pos, dW_pos[:, 0..4]
 constexpr int OE_V = 7 + 1 + OE_A + 1 + OE_P - 1;
 static_assert(OE_V == 17, "partial vector count");
 constexpr int OE_NWV = 8;          // waves (rows) per backward block
 constexpr uint32_t OE_POST_SALT = 0x5bd1e995u;   // hamt_ln_fwd's p_post stream (norm.hip)
-
-__device__ __forceinline__ float4 oe_load_x(const void* xv, size_t o, int bf16) {
-  if (bf16) {
-    const uint2 u = *(const uint2*)((const bf16_t*)xv + o);
-    return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-  }
-  return *(const float4*)((const float*)xv + o);
-}
-
-// columns c .. c+3 of ang W^T + b, W [H, 4]: one float4 per output column
-__device__ __forceinline__ float4 oe_ang(const float* __restrict__ W, const float* __restrict__ b, int c, const float (&x)[OE_A]) {
-  const float4* w = (const float4*)(W + (size_t)c * OE_A);
-  const float4 w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-  const float4 bb = *(const float4*)(b + c);
-  float4 a;
-  a.x = bb.x + x[0] * w0.x + x[1] * w0.y + x[2] * w0.z + x[3] * w0.w;
-  a.y = bb.y + x[0] * w1.x + x[1] * w1.y + x[2] * w1.z + x[3] * w1.w;
-  a.z = bb.z + x[0] * w2.x + x[1] * w2.y + x[2] * w2.z + x[3] * w2.w;
-  a.w = bb.w + x[0] * w3.x + x[1] * w3.y + x[2] * w3.z + x[3] * w3.w;
-  return a;
-}
 
 // columns c .. c+3 of pos W^T + b, W [H, 5]: the 20 weights of 4 consecutive columns are 5 aligned float4s (c % 4 == 0)
 __device__ __forceinline__ float4 oe_pos(const float* __restrict__ W, const float* __restrict__ b, int c, const float (&x)[OE_P]) {
@@ -56,21 +37,6 @@ __device__ __forceinline__ float4 oe_pos(const float* __restrict__ W, const floa
   a.z = bb.z + x[0] * q2.z + x[1] * q2.w + x[2] * q3.x + x[3] * q3.y + x[4] * q3.z;
   a.w = bb.w + x[0] * q3.w + x[1] * q4.x + x[2] * q4.y + x[3] * q4.z + x[4] * q4.w;
   return a;
-}
-
-__device__ __forceinline__ float oe_sum4(const float4 v) { return v.x + v.y + v.z + v.w; }
-__device__ __forceinline__ float oe_dot4(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-__device__ __forceinline__ float4 oe_norm(const float4 v, float m, float r) {
-  return make_float4((v.x - m) * r, (v.y - m) * r, (v.z - m) * r, (v.w - m) * r);
-}
-__device__ __forceinline__ float oe_sqdev(const float4 v, float m) {
-  const float e0 = v.x - m, e1 = v.y - m, e2 = v.z - m, e3 = v.w - m;
-  return e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-}
-
-__device__ __forceinline__ void wave_sum3(float& a, float& b, float& c) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
 }
 
 __device__ __forceinline__ void oe_row_inputs(const hamt_obj_embed_desc& d, int row, const float* __restrict__ ang,
@@ -89,11 +55,11 @@ __device__ __forceinline__ float4 oe_sum_branches(const float4 n1, const float4 
   const float4 g2 = *(const float4*)(p.gamma_ang + c), b2 = *(const float4*)(p.beta_ang + c);
   const float4 g3 = *(const float4*)(p.gamma_pos + c), b3 = *(const float4*)(p.beta_pos + c);
   const float4 tn = *(const float4*)(p.nav + c), tt = *(const float4*)(p.tt + c);
-  float4 e;
-  e.x = (((n1.x * g1.x + b1.x) + (n2.x * g2.x + b2.x)) + (n3.x * g3.x + b3.x) + tn.x) + tt.x;
-  e.y = (((n1.y * g1.y + b1.y) + (n2.y * g2.y + b2.y)) + (n3.y * g3.y + b3.y) + tn.y) + tt.y;
-  e.z = (((n1.z * g1.z + b1.z) + (n2.z * g2.z + b2.z)) + (n3.z * g3.z + b3.z) + tn.z) + tt.z;
-  e.w = (((n1.w * g1.w + b1.w) + (n2.w * g2.w + b2.w)) + (n3.w * g3.w + b3.w) + tn.w) + tt.w;
+  float4 e = affine4(n1, g1, b1);
+  acc4(e, affine4(n2, g2, b2));
+  acc4(e, affine4(n3, g3, b3));
+  acc4(e, tn);
+  acc4(e, tt);
   return e;
 }
 
@@ -107,17 +73,18 @@ __global__ __launch_bounds__(256) void obj_embed_fwd_kernel(hamt_obj_embed_desc 
   if (row >= d.M) return;
   float av[OE_A], pv[OE_P];
   oe_row_inputs(d, row, ang, pos, av, pv);
+  const int xfmt = d.x_bf16 ? LN_BF16 : LN_F32;
   float4 v[NV], a[NV], q[NV];
   float s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
-      v[i] = oe_load_x(x1, (size_t)row * H + c, d.x_bf16);
-      a[i] = oe_ang(p.w_ang, p.b_ang, c, av);
+      v[i] = load_row4(x1, (size_t)row * H + c, xfmt);
+      a[i] = angle_proj4(p.w_ang, p.b_ang, c, make_float4(av[0], av[1], av[2], av[3]));
       q[i] = oe_pos(p.w_pos, p.b_pos, c, pv);
-      s1 += oe_sum4(v[i]); s2 += oe_sum4(a[i]); s3 += oe_sum4(q[i]);
-    } else { v[i] = make_float4(0.f, 0.f, 0.f, 0.f); a[i] = v[i]; q[i] = v[i]; }
+      s1 += sum4(v[i]); s2 += sum4(a[i]); s3 += sum4(q[i]);
+    } else { v[i] = zero4(); a[i] = v[i]; q[i] = v[i]; }
   }
   wave_sum3(s1, s2, s3);
   const float inv_h = 1.0f / (float)H;
@@ -125,7 +92,7 @@ __global__ __launch_bounds__(256) void obj_embed_fwd_kernel(hamt_obj_embed_desc 
   float t1 = 0.f, t2 = 0.f, t3 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
-    if ((i * 64 + lane) * 4 < H) { t1 += oe_sqdev(v[i], m1); t2 += oe_sqdev(a[i], m2); t3 += oe_sqdev(q[i], m3); }
+    if ((i * 64 + lane) * 4 < H) { t1 += sqdev4(v[i], m1); t2 += sqdev4(a[i], m2); t3 += sqdev4(q[i], m3); }
   wave_sum3(t1, t2, t3);
   const float r1 = rsqrtf(t1 * inv_h + d.eps_img), r2 = rsqrtf(t2 * inv_h + d.eps_ang), r3 = rsqrtf(t3 * inv_h + d.eps_pos);
   float s4 = 0.f;
@@ -133,8 +100,8 @@ __global__ __launch_bounds__(256) void obj_embed_fwd_kernel(hamt_obj_embed_desc 
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
-      v[i] = oe_sum_branches(oe_norm(v[i], m1, r1), oe_norm(a[i], m2, r2), oe_norm(q[i], m3, r3), p, c);
-      s4 += oe_sum4(v[i]);
+      v[i] = oe_sum_branches(norm4(v[i], m1, r1), norm4(a[i], m2, r2), norm4(q[i], m3, r3), p, c);
+      s4 += sum4(v[i]);
     }
   }
   s4 = wave_sum(s4);
@@ -142,24 +109,17 @@ __global__ __launch_bounds__(256) void obj_embed_fwd_kernel(hamt_obj_embed_desc 
   float t4 = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
-    if ((i * 64 + lane) * 4 < H) t4 += oe_sqdev(v[i], m4);
+    if ((i * 64 + lane) * 4 < H) t4 += sqdev4(v[i], m4);
   t4 = wave_sum(t4);
   const float r4 = rsqrtf(t4 * inv_h + d.eps_out);
   const RngKey kd = rng_key(rng, d.call_id ^ OE_POST_SALT);
   const float ik = d.p_drop > 0.f ? 1.0f / (1.0f - d.p_drop) : 1.0f;
-  const uint32_t rowh = hamt_mix32((uint32_t)row ^ kd.k0);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
-      const float4 g = *(const float4*)(p.gamma_out + c), b = *(const float4*)(p.beta_out + c);
-      float4 r;
-      r.x = (v[i].x - m4) * r4 * g.x + b.x; r.y = (v[i].y - m4) * r4 * g.y + b.y;
-      r.z = (v[i].z - m4) * r4 * g.z + b.z; r.w = (v[i].w - m4) * r4 * g.w + b.w;
-      if (d.p_drop > 0.f) {
-        float f_[4]; drop_scale4(kd, rowh, (uint32_t)(c >> 2), d.p_drop, ik, f_);
-        r.x *= f_[0]; r.y *= f_[1]; r.z *= f_[2]; r.w *= f_[3];
-      }
+      float4 r = affine4(norm4(v[i], m4, r4), *(const float4*)(p.gamma_out + c), *(const float4*)(p.beta_out + c));
+      if (d.p_drop > 0.f) r = mul4(r, keep4(kd, row, c, d.p_drop, ik));
       *(float4*)(y + (size_t)row * H + c) = r;
     }
   }
@@ -168,13 +128,6 @@ __global__ __launch_bounds__(256) void obj_embed_fwd_kernel(hamt_obj_embed_desc 
     stats[row] = m1; stats[M + row] = r1; stats[2 * M + row] = m2; stats[3 * M + row] = r2;
     stats[4 * M + row] = m3; stats[5 * M + row] = r3; stats[6 * M + row] = m4; stats[7 * M + row] = r4;
   }
-}
-
-__device__ __forceinline__ float4 oe_mul(const float4 a, const float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-__device__ __forceinline__ float4 oe_scale(const float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
-// LayerNorm backward of one row given u = dy * gamma, the normalised input n, their wave means cu / eu and rstd r
-__device__ __forceinline__ float4 oe_ln_dx(const float4 u, const float4 n, float cu, float eu, float r) {
-  return make_float4(r * (u.x - cu - n.x * eu), r * (u.y - cu - n.y * eu), r * (u.z - cu - n.z * eu), r * (u.w - cu - n.w * eu));
 }
 
 // one row per wave, OE_NWV rows per block; the block's 17 column-sum contributions go to ws[block][17][H]
@@ -187,13 +140,11 @@ __global__ __launch_bounds__(64 * OE_NWV) void obj_embed_bwd_kernel(hamt_obj_emb
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int H = d.H;
   const size_t M = d.M;
-  if (dx16 && blockIdx.x == 0)      // zero the reduction-padding rows [M, Mpad16) of the bf16 gradient image
-    for (int r = d.M + w; r < d.Mpad16; r += OE_NWV)
-      for (int c = lane * 4; c < H; c += 256) *(uint2*)(dx16 + (size_t)r * H + c) = make_uint2(0u, 0u);
+  if (dx16 && blockIdx.x == 0) zero_pad_rows(dx16, H, d.M + w, d.Mpad16, OE_NWV, lane);
   const int row = blockIdx.x * OE_NWV + w;
   const bool live = row < d.M;      // (no early return: every wave takes part in the block reduction below)
   float av[OE_A] = {0.f, 0.f, 0.f, 0.f}, pv[OE_P] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 z4 = zero4();
   float4 dyo[NV], no[NV], de[NV], n1[NV], n2[NV], n3[NV], d2[NV], d3[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) { dyo[i] = z4; no[i] = z4; de[i] = z4; n1[i] = z4; n2[i] = z4; n3[i] = z4; d2[i] = z4; d3[i] = z4; }
@@ -203,26 +154,23 @@ __global__ __launch_bounds__(64 * OE_NWV) void obj_embed_bwd_kernel(hamt_obj_emb
     const float m3 = stats[4 * M + row], r3 = stats[5 * M + row], m4 = stats[6 * M + row], r4 = stats[7 * M + row];
     const RngKey kd = rng_key(rng, d.call_id ^ OE_POST_SALT);
     const float ik = d.p_drop > 0.f ? 1.0f / (1.0f - d.p_drop) : 1.0f;
-    const uint32_t rowh = hamt_mix32((uint32_t)row ^ kd.k0);
-    const float inv_h = 1.0f / (float)H;
+      const float inv_h = 1.0f / (float)H;
+    const int xfmt = d.x_bf16 ? LN_BF16 : LN_F32;
     float su = 0.f, tu = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
       if (c < H) {
         const size_t o = (size_t)row * H + c;
-        n1[i] = oe_norm(oe_load_x(x1, o, d.x_bf16), m1, r1);
-        n2[i] = oe_norm(oe_ang(p.w_ang, p.b_ang, c, av), m2, r2);
-        n3[i] = oe_norm(oe_pos(p.w_pos, p.b_pos, c, pv), m3, r3);
-        no[i] = oe_norm(oe_sum_branches(n1[i], n2[i], n3[i], p, c), m4, r4);
+        n1[i] = norm4(load_row4(x1, o, xfmt), m1, r1);
+        n2[i] = norm4(angle_proj4(p.w_ang, p.b_ang, c, make_float4(av[0], av[1], av[2], av[3])), m2, r2);
+        n3[i] = norm4(oe_pos(p.w_pos, p.b_pos, c, pv), m3, r3);
+        no[i] = norm4(oe_sum_branches(n1[i], n2[i], n3[i], p, c), m4, r4);
         float4 g = *(const float4*)(dy + o);
-        if (d.p_drop > 0.f) {
-          float f_[4]; drop_scale4(kd, rowh, (uint32_t)(c >> 2), d.p_drop, ik, f_);
-          g.x *= f_[0]; g.y *= f_[1]; g.z *= f_[2]; g.w *= f_[3];
-        }
+        if (d.p_drop > 0.f) g = mul4(g, keep4(kd, row, c, d.p_drop, ik));
         dyo[i] = g;
-        const float4 u = oe_mul(g, *(const float4*)(p.gamma_out + c));
-        su += oe_sum4(u); tu += oe_dot4(u, no[i]);
+        const float4 u = mul4(g, *(const float4*)(p.gamma_out + c));
+        su += sum4(u); tu += dot4(u, no[i]);
       }
     }
     su = wave_sum(su); tu = wave_sum(tu);
@@ -231,13 +179,13 @@ __global__ __launch_bounds__(64 * OE_NWV) void obj_embed_bwd_kernel(hamt_obj_emb
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
       if (c < H) {
-        de[i] = oe_ln_dx(oe_mul(dyo[i], *(const float4*)(p.gamma_out + c)), no[i], su * inv_h, tu * inv_h, r4);
-        const float4 u1 = oe_mul(de[i], *(const float4*)(p.gamma_img + c));
-        const float4 u2 = oe_mul(de[i], *(const float4*)(p.gamma_ang + c));
-        const float4 u3 = oe_mul(de[i], *(const float4*)(p.gamma_pos + c));
-        s1 += oe_sum4(u1); t1 += oe_dot4(u1, n1[i]);
-        s2 += oe_sum4(u2); t2 += oe_dot4(u2, n2[i]);
-        s3 += oe_sum4(u3); t3 += oe_dot4(u3, n3[i]);
+        de[i] = ln_dx4(mul4(dyo[i], *(const float4*)(p.gamma_out + c)), no[i], su * inv_h, tu * inv_h, r4);
+        const float4 u1 = mul4(de[i], *(const float4*)(p.gamma_img + c));
+        const float4 u2 = mul4(de[i], *(const float4*)(p.gamma_ang + c));
+        const float4 u3 = mul4(de[i], *(const float4*)(p.gamma_pos + c));
+        s1 += sum4(u1); t1 += dot4(u1, n1[i]);
+        s2 += sum4(u2); t2 += dot4(u2, n2[i]);
+        s3 += sum4(u3); t3 += dot4(u3, n3[i]);
       }
     }
     wave_sum3(s1, s2, s3);
@@ -247,70 +195,41 @@ __global__ __launch_bounds__(64 * OE_NWV) void obj_embed_bwd_kernel(hamt_obj_emb
       const int c = (i * 64 + lane) * 4;
       if (c < H) {
         const size_t o = (size_t)row * H + c;
-        const float4 r = oe_ln_dx(oe_mul(de[i], *(const float4*)(p.gamma_img + c)), n1[i], s1 * inv_h, t1 * inv_h, r1);
+        const float4 r = ln_dx4(mul4(de[i], *(const float4*)(p.gamma_img + c)), n1[i], s1 * inv_h, t1 * inv_h, r1);
         if (dx) *(float4*)(dx + o) = r;
-        if (dx16) *(uint2*)(dx16 + o) = make_uint2(pack_bf2(r.x, r.y), pack_bf2(r.z, r.w));
-        d2[i] = oe_ln_dx(oe_mul(de[i], *(const float4*)(p.gamma_ang + c)), n2[i], s2 * inv_h, t2 * inv_h, r2);
-        d3[i] = oe_ln_dx(oe_mul(de[i], *(const float4*)(p.gamma_pos + c)), n3[i], s3 * inv_h, t3 * inv_h, r3);
+        if (dx16) store_bf4(dx16, o, r);
+        d2[i] = ln_dx4(mul4(de[i], *(const float4*)(p.gamma_ang + c)), n2[i], s2 * inv_h, t2 * inv_h, r2);
+        d3[i] = ln_dx4(mul4(de[i], *(const float4*)(p.gamma_pos + c)), n3[i], s3 * inv_h, t3 * inv_h, r3);
       }
     }
   }
   // block sums of the 17 contributions, one vector at a time through LDS (a dead wave contributes zeros), waves in a fixed order
-  __shared__ float4 red[OE_NWV][NV * 64];
 #pragma unroll
   for (int v = 0; v < OE_V; ++v) {
+    float4 t[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      float4 t;
-      if (v == 0) t = oe_mul(dyo[i], no[i]);
-      else if (v == 1) t = dyo[i];
-      else if (v == 2) t = de[i];
-      else if (v == 3) t = oe_mul(de[i], n1[i]);
-      else if (v == 4) t = oe_mul(de[i], n2[i]);
-      else if (v == 5) t = oe_mul(de[i], n3[i]);
-      else if (v == 6) t = d2[i];
-      else if (v < 7 + OE_A) t = oe_scale(d2[i], av[v - 7]);
-      else if (v == 7 + OE_A) t = d3[i];
-      else t = oe_scale(d3[i], pv[v - 8 - OE_A]);
-      red[w][i * 64 + lane] = t;
+      if (v == 0) t[i] = mul4(dyo[i], no[i]);
+      else if (v == 1) t[i] = dyo[i];
+      else if (v == 2) t[i] = de[i];
+      else if (v == 3) t[i] = mul4(de[i], n1[i]);
+      else if (v == 4) t[i] = mul4(de[i], n2[i]);
+      else if (v == 5) t[i] = mul4(de[i], n3[i]);
+      else if (v == 6) t[i] = d2[i];
+      else if (v < 7 + OE_A) t[i] = scale4(d2[i], av[v - 7]);
+      else if (v == 7 + OE_A) t[i] = d3[i];
+      else t[i] = scale4(d3[i], pv[v - 8 - OE_A]);
     }
-    __syncthreads();
-    for (int e = threadIdx.x; e < NV * 64; e += 64 * OE_NWV) {
-      const int c = e * 4;
-      if (c < H) {
-        float4 t = red[0][e];
-#pragma unroll
-        for (int k = 1; k < OE_NWV; ++k) { const float4 r = red[k][e]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
-        *(float4*)(ws + ((size_t)blockIdx.x * OE_V + v) * H + c) = t;
-      }
-    }
-    __syncthreads();
+    block_partial<NV, OE_NWV>(t, ws, (size_t)blockIdx.x * OE_V + v, H);
   }
 }
 
 // ws[nb][17][H] -> the gradients (ADDED to what is there).  block = 64 columns (16 float4 lanes) x 16 partial-row phases.
 __global__ __launch_bounds__(256) void obj_embed_reduce_kernel(int nb, int H, const float* __restrict__ ws, hamt_obj_embed_grads g) {
-  const int l16 = threadIdx.x & 15, ph = threadIdx.x >> 4;
   const int per = H / 64;                          // blocks per vector
-  const int v = blockIdx.x / per, col = (blockIdx.x % per) * 64 + l16 * 4;
-  float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int b0 = ph; b0 < nb; b0 += 64) {           // 4 independent loads per trip
-    float4 q[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int b = b0 + 16 * u;
-      q[u] = b < nb ? *(const float4*)(ws + ((size_t)b * OE_V + v) * H + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { t.x += q[u].x; t.y += q[u].y; t.z += q[u].z; t.w += q[u].w; }
-  }
-  __shared__ float4 red[16][16];
-  red[ph][l16] = t;
-  __syncthreads();
-  if (ph != 0) return;
-  t = red[0][l16];
-#pragma unroll
-  for (int i = 1; i < 16; ++i) { const float4 r = red[i][l16]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
+  const int v = blockIdx.x / per, col = (blockIdx.x % per) * 64 + (threadIdx.x & 15) * 4;
+  float4 t;
+  if (!reduce_partials(ws + (size_t)v * H + col, (size_t)OE_V * H, nb, t)) return;
   const float e[4] = {t.x, t.y, t.z, t.w};
   float* dst[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int stride = 1, off = 0;
@@ -341,8 +260,8 @@ bool oe_aligned(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
 
 int oe_check(const hamt_obj_embed_desc* d, const hamt_obj_embed_params* p, const char* who) {
   HAMT_CHECK_ARG(d && p, "%s: null pointer", who);
-  HAMT_CHECK_ARG(d->H % 64 == 0 && d->H >= 64 && d->H <= 1024, "%s: H=%d unsupported (need H%%64==0, H<=1024)", who, d->H);
-  HAMT_CHECK_ARG(d->A == OE_A && d->ld_ang >= OE_A, "%s: angle features %d (ld %d): only 4 is built", who, d->A, d->ld_ang);
+  if (int rc = ln_row_check_h(d->H, who)) return rc;
+  if (int rc = ln_row_check_angle(d->A, d->ld_ang, 1, who)) return rc;      // (rows are read element by element)
   HAMT_CHECK_ARG(d->P == OE_P && d->ld_pos >= OE_P, "%s: position features %d (ld %d): only 5 is built", who, d->P, d->ld_pos);
   HAMT_CHECK_ARG(d->M >= 0 && d->p_drop >= 0.f && d->p_drop < 1.f, "%s: bad M=%d or dropout p=%g", who, d->M, (double)d->p_drop);
   const void* ps[14] = {p->w_ang, p->b_ang, p->w_pos, p->b_pos, p->gamma_img, p->beta_img, p->gamma_ang, p->beta_ang, p->gamma_pos,
@@ -364,11 +283,10 @@ extern "C" int hamt_obj_embed_fwd(const hamt_obj_embed_desc* d, const hamt_obj_e
   HAMT_CHECK_ARG(x1 && ang && pos && y && stats, "hamt_obj_embed_fwd: null pointer");
   HAMT_CHECK_ARG(oe_aligned(x1) && oe_aligned(y), "hamt_obj_embed_fwd: x1 / y not 16-byte aligned");
   if (d->M == 0) return HAMT_OK;
-  const int nv = (d->H + 255) / 256;
   dim3 grid((d->M + 3) / 4), block(256);
   hipStream_t s = (hipStream_t)stream;
 #define LAUNCH(NV) hipLaunchKernelGGL((obj_embed_fwd_kernel<NV>), grid, block, 0, s, *d, *p, x1, ang, pos, y, stats, rng)
-  switch (nv) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+  LN_ROW_DISPATCH(d->H, LAUNCH)
 #undef LAUNCH
   HAMT_CHECK_LAUNCH("hamt_obj_embed_fwd");
   return HAMT_OK;
@@ -384,10 +302,9 @@ extern "C" int hamt_obj_embed_bwd(const hamt_obj_embed_desc* d, const hamt_obj_e
   HAMT_CHECK_ARG(!dx16 || d->Mpad16 >= d->M, "hamt_obj_embed_bwd: Mpad16 %d < M %d", d->Mpad16, d->M);
   if (d->M == 0) return HAMT_OK;
   const int nb = oe_blocks(d->M);
-  const int nv = (d->H + 255) / 256;
   hipStream_t s = (hipStream_t)stream;
 #define LAUNCH(NV) hipLaunchKernelGGL((obj_embed_bwd_kernel<NV>), dim3(nb), dim3(64 * OE_NWV), 0, s, *d, *p, dy, x1, ang, pos, stats, dx, (bf16_t*)dx16, ws, rng)
-  switch (nv) { case 1: LAUNCH(1); break; case 2: LAUNCH(2); break; case 3: LAUNCH(3); break; default: LAUNCH(4); }
+  LN_ROW_DISPATCH(d->H, LAUNCH)
 #undef LAUNCH
   HAMT_CHECK_LAUNCH("hamt_obj_embed_bwd");
   hipLaunchKernelGGL(obj_embed_reduce_kernel, dim3(OE_V * (d->H / 64)), dim3(256), 0, s, nb, d->H, ws, *g);
