@@ -502,6 +502,39 @@ int hamt_a2c_fwd(int T, int B, const float* reward, const float* mask, const flo
                  const float* last_value, float gamma, float ent_w, float* ret, float* out, void* stream);
 int hamt_a2c_bwd(int T, int B, const float* ret, const float* mask, const float* value, float ent_w, const float* g,
                  float* dlogp, float* dvalue, float* dent, void* stream);
+/* The decision and loss side of ONE rollout step of the finetune agents (finetune_src/r2r/agent_cmt.py:336-401; the R2R-back, CVDN
+ * and REVERIE agents repeat it verbatim), all B episodes in one launch, one wave per row of logit [B, V <= 256] (fp32, row stride
+ * ld_logit, -inf entries allowed).  Per row b, written at the caller's row-t addresses of its [T, B] arrays (what hamt_a2c_fwd reads):
+ *   ml      cross-entropy of the UNMASKED row against target[b] (:339), 0 where target == ignoreid or target is NULL
+ *   action  a_t: forced_action[b] if given; else target (teacher), the lowest index among the maxima of the back-track-masked row
+ *           (argmax, :356), or the inverse CDF of the masked softmax at uniform[b] (sample; uniform NULL: a 24-bit draw hashed
+ *           from rng = {seed, epoch} (DEVICE, as every dropout kernel reads it), call_id and b)
+ *   logp    teacher 0; argmax log_softmax(masked row)[a_t] (:358-359); sample the same clamped to [log eps, log(1 - eps)],
+ *           eps = FLT_EPSILON, as torch.distributions.Categorical(probs).log_prob does (:361-366)
+ *   ent     -sum p log p of the masked row, 0 log 0 = 0; written in sample mode only (:364)
+ *   mask    !ended_in (:418-420);   env_action  -1 if a_t == cand_len - 1 (STOP), a_t == ignoreid or ended_in, else a_t (:372-375)
+ *   prev_angle [B, A] = ob_ang[b, env_action, :] (ob_ang [B, V, A] contiguous), zeros where env_action == -1 or ob_ang is NULL (:382-385)
+ *   ended   (in/out, uint8) |= env_action == -1 (:447);   hist_len (in/out, may be NULL) += !ended_in (:399-401)
+ *   lse [B, 2]  log-sum-exp of the unmasked and of the masked row: all the backward needs next to the inputs
+ * bt_mask [B, V] uint8 (non-zero = masked, :350), target, ob_ang, forced_action, uniform, prev_angle, hist_len may be NULL.
+ * A row whose every slot is masked cannot occur on the path (the STOP slot is never a visited viewpoint); it, and an action outside
+ * [0, V), give env_action -1, logp 0, ent 0 and zero gradients, never NaN or an out-of-bounds read.
+ * bwd: dlogit[b, v] = g_ml[b] (softmax(logit)[v] - [v == target]) + g_logp[b] ([v == a_t] - p[v]) + g_ent[b] (-p[v] (log p[v] + H[b])),
+ * p the masked softmax; the last two terms are 0 at masked positions, the first for ignored rows, the second where the clamp was
+ * active.  g_ml / g_logp / g_ent may be NULL (= 0); row b of each is read at element b * gs_* (1 = contiguous, 0 = one value for
+ * every row: the expanded gradient of a plain sum arrives like that, and needs no copy). */
+#define HAMT_POLICY_TEACHER 0
+#define HAMT_POLICY_ARGMAX 1
+#define HAMT_POLICY_SAMPLE 2
+int hamt_policy_step_fwd(int B, int V, int A, int mode, int64_t ignoreid, const float* logit, int ld_logit,
+                         const int64_t* target, const uint8_t* bt_mask, const int32_t* cand_len, uint8_t* ended,
+                         const float* ob_ang, const int64_t* forced_action, const float* uniform, const uint64_t* rng,
+                         uint32_t call_id, float* ml, int64_t* action, float* logp, float* ent, float* mask,
+                         int32_t* env_action, float* prev_angle, int32_t* hist_len, float* lse, void* stream);
+int hamt_policy_step_bwd(int B, int V, int mode, int64_t ignoreid, const float* logit, int ld_logit, const int64_t* target,
+                         const uint8_t* bt_mask, const int64_t* action, const float* lse, const float* g_ml,
+                         const float* g_logp, const float* g_ent, int gs_ml, int gs_logp, int gs_ent, float* dlogit, int ld_dlogit,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

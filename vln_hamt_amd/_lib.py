@@ -157,6 +157,8 @@ SIGNATURES = {
     "hamt_debug_wgrad_times": [vp, vp, vp, C.c_int],
     "hamt_a2c_fwd": [i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp],
     "hamt_a2c_bwd": [i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp],
+    "hamt_policy_step_fwd": [i32, i32, i32, i32, C.c_int64, vp, i32] + [vp] * 8 + [u32] + [vp] * 10,
+    "hamt_policy_step_bwd": [i32, i32, i32, C.c_int64, vp, i32] + [vp] * 7 + [i32, i32, i32, vp, i32, vp],
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

@@ -1,0 +1,264 @@
+// The decision and loss side of ONE rollout step of the finetune agents (finetune_src/r2r/agent_cmt.py:336-401, repeated verbatim by
+// the R2R-back, CVDN and REVERIE agents), for all B episodes in one launch:
+//   imitation cross-entropy on the raw logits (:339)  ->  back-track mask (:350)  ->  teacher / argmax / sample choice with its
+//   log-probability and entropy (:353-366)  ->  environment action (:372-375), the chosen candidate's angle feature (:382-385),
+//   `ended` (:447), the A2C mask (:418-420) and the history lengths (:399-401).
+// One wave per row, lanes strided over the V <= 256 columns (4 per lane, held in registers), wave reductions only: no LDS, no atomics,
+// no hand-off between rows.  Every per-row result is stored by lane 0 with ordinary (vector) stores.
+#include "common.h"
+#include <float.h>
+
+namespace {
+
+constexpr int kCols = 4;                 // columns per lane: V <= 64 * kCols
+constexpr int kRowsPerBlock = 4;         // waves per 256-thread workgroup
+
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// exp(x - ref) with exp(-inf - anything) = 0 (never -inf - -inf = NaN)
+__device__ __forceinline__ float exp_rel(float x, float ref) { return x == -INFINITY ? 0.f : expf(x - ref); }
+
+// max and sum of exp(x - max) over the row; a row of -inf gives m = -inf, s = 0
+__device__ __forceinline__ void row_max_sum(const float (&x)[kCols], float& m, float& s) {
+  m = wave_max(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
+  s = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) s += exp_rel(x[k], m);
+  s = wave_sum(s);
+}
+__device__ __forceinline__ float lse_of(float m, float s) { return m == -INFINITY ? -INFINITY : m + logf(s); }
+
+__device__ __forceinline__ void load_row(const float* __restrict__ xr, const uint8_t* __restrict__ mr, int V, int lane,
+                                         float (&x)[kCols], float (&xm)[kCols]) {
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    const int v = lane + 64 * k;
+    x[k] = v < V ? xr[v] : -INFINITY;
+    xm[k] = (mr && v < V && mr[v]) ? -INFINITY : x[k];
+  }
+}
+
+// log pi(a) of the masked row as the reference takes it: log_softmax(...).gather (argmax, :358-359) or Categorical(probs).log_prob
+// (sample, :361-366: probabilities clamped to [eps, 1 - eps] before the log).  `live` = the gradient flows (no clamp, a real slot).
+__device__ __forceinline__ float chosen_logp(int mode, float xa, float lse1, bool a_ok, bool& live) {
+  live = false;
+  if (mode == HAMT_POLICY_TEACHER || !a_ok || lse1 == -INFINITY) return 0.f;
+  float lp = xa == -INFINITY ? -INFINITY : xa - lse1;
+  live = xa != -INFINITY;
+  if (mode == HAMT_POLICY_SAMPLE) {
+    const float lo = logf(FLT_EPSILON), hi = logf(1.0f - FLT_EPSILON);
+    if (lp < lo) { lp = lo; live = false; }
+    if (lp > hi) { lp = hi; live = false; }
+  }
+  return lp;
+}
+
+__global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_fwd_kernel(
+    int B, int V, int A, int mode, long long ignoreid, const float* __restrict__ logit, int ld, const int64_t* __restrict__ target,
+    const uint8_t* __restrict__ bt_mask, const int32_t* __restrict__ cand_len, uint8_t* ended, const float* __restrict__ ob_ang,
+    const int64_t* __restrict__ forced, const float* __restrict__ uniform, const uint64_t* __restrict__ rng, uint32_t call_id,
+    float* __restrict__ ml, int64_t* __restrict__ action, float* __restrict__ logp, float* __restrict__ ent, float* __restrict__ mask,
+    int32_t* __restrict__ env_action, float* __restrict__ prev_angle, int32_t* hist_len, float* __restrict__ lse) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;                                       // (whole waves leave: nothing below synchronises a workgroup)
+  const float* xr = logit + (size_t)b * ld;
+  const uint8_t* mr = bt_mask ? bt_mask + (size_t)b * V : nullptr;
+  float x[kCols], xm[kCols];
+  load_row(xr, mr, V, lane, x, xm);
+
+  // ---- imitation cross-entropy on the UNMASKED row (:339 precedes :350)
+  float m0, s0;
+  row_max_sum(x, m0, s0);
+  const float lse0 = lse_of(m0, s0);
+  const long long tgt = target ? (long long)target[b] : ignoreid;
+  float ml_b = 0.f;
+  if (tgt != ignoreid) ml_b = (tgt >= 0 && tgt < V) ? lse0 - xr[tgt] : __builtin_nanf("");    // (a target behind the row: NaN, as hamt_ce_fwd)
+
+  // ---- the distribution the action comes from: the back-track-masked row
+  float m1 = m0, s1 = s0;
+  if (mr) row_max_sum(xm, m1, s1);
+  const float lse1 = lse_of(m1, s1);
+  const bool dead = m1 == -INFINITY;                        // every slot masked: cannot occur on the path (the STOP slot is never visited)
+
+  long long a;
+  if (forced) {
+    a = (long long)forced[b];
+  } else if (mode == HAMT_POLICY_TEACHER) {
+    a = tgt;
+  } else if (mode == HAMT_POLICY_ARGMAX) {
+    int first = V;                                          // lowest index among the maxima (torch.max's tie rule on one device)
+#pragma unroll
+    for (int k = kCols - 1; k >= 0; --k) {
+      const int v = lane + 64 * k;
+      if (v < V && xm[k] == m1) first = v;
+    }
+    a = wave_min_i(first);
+    if (a >= V) a = 0;
+  } else {
+    float u;
+    if (uniform) {
+      u = uniform[b];
+    } else {                                                // counter hash of (seed, epoch, call_id, row): 24-bit uniform in [0, 1)
+      const RngKey key = rng_key(rng, call_id);
+      uint32_t h = hamt_mix32((uint32_t)b ^ key.k0);
+      h = hamt_mix32(h + key.k1);
+      u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    }
+    // inverse CDF: the first slot of non-zero probability whose inclusive cumulative probability exceeds u (the fp32 wave scan is not
+    // guaranteed monotone to the last bit: a slot of probability 0 is never taken, whatever its rounded sum says); none: the last such slot
+    const float inv_s = dead ? 0.f : 1.0f / s1;
+    float base = 0.f;
+    int first = 0x7fffffff, last = -1;
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) {
+      if (64 * k < V) {                                     // (wave-uniform)
+        const int v = lane + 64 * k;
+        const float e = exp_rel(xm[k], m1);
+        float scan = e;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const float up = __shfl_up(scan, o, 64);
+          if (lane >= o) scan += up;
+        }
+        if (e > 0.f) {
+          last = v;
+          if (first == 0x7fffffff && (base + scan) * inv_s > u) first = v;
+        }
+        base += __shfl(scan, 63, 64);
+      }
+    }
+    first = wave_min_i(first);
+    last = wave_max_i(last);
+    a = first != 0x7fffffff ? first : last;
+    if (a < 0) a = 0;
+  }
+
+  // ---- log pi(a_t), entropy
+  const bool a_ok = a >= 0 && a < V;
+  float xa = -INFINITY;
+  if (a_ok) xa = (mr && mr[a]) ? -INFINITY : xr[a];
+  bool live;
+  const float lp = chosen_logp(mode, xa, lse1, a_ok, live);
+  float H = 0.f;
+  if (mode == HAMT_POLICY_SAMPLE) {
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) {
+      const float p = exp_rel(xm[k], lse1);
+      if (p > 0.f) H -= p * (xm[k] - lse1);                  // 0 log 0 = 0
+    }
+    H = wave_sum(H);
+    if (dead) H = 0.f;
+  }
+
+  // ---- environment action, previous-action angle, book-keeping
+  const bool was_ended = ended[b] != 0;
+  const int cl = cand_len[b];
+  int env = -1;
+  if (a_ok && !dead && !was_ended && a != ignoreid && a != (long long)cl - 1) env = (int)a;
+  if (prev_angle) {
+    for (int j = lane; j < A; j += 64)
+      prev_angle[(size_t)b * A + j] = (env >= 0 && ob_ang) ? ob_ang[((size_t)b * V + env) * A + j] : 0.f;
+  }
+  if (lane == 0) {
+    ml[b] = ml_b;
+    action[b] = (int64_t)a;
+    logp[b] = lp;
+    if (mode == HAMT_POLICY_SAMPLE && ent) ent[b] = H;
+    mask[b] = was_ended ? 0.f : 1.f;
+    env_action[b] = env;
+    ended[b] = (was_ended || env < 0) ? 1 : 0;
+    if (hist_len && !was_ended) hist_len[b] += 1;
+    lse[2 * b] = lse0;
+    lse[2 * b + 1] = lse1;
+  }
+}
+
+__global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_bwd_kernel(
+    int B, int V, int mode, long long ignoreid, const float* __restrict__ logit, int ld, const int64_t* __restrict__ target,
+    const uint8_t* __restrict__ bt_mask, const int64_t* __restrict__ action, const float* __restrict__ lse, const float* __restrict__ g_ml,
+    const float* __restrict__ g_logp, const float* __restrict__ g_ent, int gs_ml, int gs_logp, int gs_ent, float* __restrict__ dlogit, int ldd) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const float* xr = logit + (size_t)b * ld;
+  const uint8_t* mr = bt_mask ? bt_mask + (size_t)b * V : nullptr;
+  float x[kCols], xm[kCols];
+  load_row(xr, mr, V, lane, x, xm);
+  const float lse0 = lse[2 * b], lse1 = lse[2 * b + 1];
+  const long long tgt = target ? (long long)target[b] : ignoreid;
+  const long long a = (long long)action[b];
+  const bool a_ok = a >= 0 && a < V;
+  float xa = -INFINITY;
+  if (a_ok) xa = (mr && mr[a]) ? -INFINITY : xr[a];
+  bool live;
+  chosen_logp(mode, xa, lse1, a_ok, live);
+  const bool dead = lse1 == -INFINITY;
+  const float gm = (g_ml && tgt != ignoreid) ? g_ml[(size_t)b * gs_ml] : 0.f;
+  const float bad = (tgt != ignoreid && !(tgt >= 0 && tgt < V)) ? __builtin_nanf("") : 0.f;
+  const float gl = (g_logp && live && mode != HAMT_POLICY_TEACHER) ? g_logp[(size_t)b * gs_logp] : 0.f;
+  const bool with_ent = g_ent && mode == HAMT_POLICY_SAMPLE && !dead;
+  const float ge = with_ent ? g_ent[(size_t)b * gs_ent] : 0.f;
+  float p1[kCols], H = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    p1[k] = dead ? 0.f : exp_rel(xm[k], lse1);
+    if (p1[k] > 0.f) H -= p1[k] * (xm[k] - lse1);
+  }
+  if (with_ent) H = wave_sum(H);                            // (wave-uniform condition)
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    const int v = lane + 64 * k;
+    if (v < V) {
+      float d = 0.f;
+      if (tgt != ignoreid) d = gm * (exp_rel(x[k], lse0) - (v == tgt ? 1.f : 0.f)) + bad;
+      if (xm[k] != -INFINITY) {                             // masked (and -inf) positions take nothing from the last two terms
+        if (gl != 0.f) d += gl * ((v == a ? 1.f : 0.f) - p1[k]);
+        if (with_ent && p1[k] > 0.f) d += ge * (-p1[k] * ((xm[k] - lse1) + H));
+      }
+      dlogit[(size_t)b * ldd + v] = d;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int hamt_policy_step_fwd(int B, int V, int A, int mode, int64_t ignoreid, const float* logit, int ld_logit,
+                                    const int64_t* target, const uint8_t* bt_mask, const int32_t* cand_len, uint8_t* ended,
+                                    const float* ob_ang, const int64_t* forced_action, const float* uniform, const uint64_t* rng,
+                                    uint32_t call_id, float* ml, int64_t* action, float* logp, float* ent, float* mask,
+                                    int32_t* env_action, float* prev_angle, int32_t* hist_len, float* lse, void* stream) {
+  HAMT_CHECK_ARG(B >= 0 && V > 0 && V <= 64 * kCols && A >= 0 && ld_logit >= V, "hamt_policy_step_fwd: need 0 < V <= 256, ld_logit >= V");
+  HAMT_CHECK_ARG(mode == HAMT_POLICY_TEACHER || mode == HAMT_POLICY_ARGMAX || mode == HAMT_POLICY_SAMPLE, "hamt_policy_step_fwd: bad mode");
+  HAMT_CHECK_ARG(logit && cand_len && ended && ml && action && logp && mask && env_action && lse, "hamt_policy_step_fwd: null pointer");
+  HAMT_CHECK_ARG(mode != HAMT_POLICY_SAMPLE || ent, "hamt_policy_step_fwd: sample mode writes ent");
+  HAMT_CHECK_ARG(mode != HAMT_POLICY_TEACHER || target || forced_action, "hamt_policy_step_fwd: teacher mode needs a target");
+  if (B == 0) return HAMT_OK;
+  hipLaunchKernelGGL(policy_step_fwd_kernel, dim3((B + kRowsPerBlock - 1) / kRowsPerBlock), dim3(64 * kRowsPerBlock), 0, as_stream(stream),
+                     B, V, A, mode, (long long)ignoreid, logit, ld_logit, target, bt_mask, cand_len, ended, ob_ang, forced_action, uniform,
+                     rng, call_id, ml, action, logp, ent, mask, env_action, prev_angle, hist_len, lse);
+  HAMT_CHECK_LAUNCH("hamt_policy_step_fwd");
+  return HAMT_OK;
+}
+
+extern "C" int hamt_policy_step_bwd(int B, int V, int mode, int64_t ignoreid, const float* logit, int ld_logit, const int64_t* target,
+                                    const uint8_t* bt_mask, const int64_t* action, const float* lse, const float* g_ml,
+                                    const float* g_logp, const float* g_ent, int gs_ml, int gs_logp, int gs_ent, float* dlogit, int ld_dlogit,
+                                    void* stream) {
+  HAMT_CHECK_ARG(B >= 0 && V > 0 && V <= 64 * kCols && ld_logit >= V && ld_dlogit >= V, "hamt_policy_step_bwd: need 0 < V <= 256, ld >= V");
+  HAMT_CHECK_ARG(logit && action && lse && dlogit, "hamt_policy_step_bwd: null pointer");
+  HAMT_CHECK_ARG(gs_ml >= 0 && gs_logp >= 0 && gs_ent >= 0, "hamt_policy_step_bwd: negative gradient stride");
+  if (B == 0) return HAMT_OK;
+  hipLaunchKernelGGL(policy_step_bwd_kernel, dim3((B + kRowsPerBlock - 1) / kRowsPerBlock), dim3(64 * kRowsPerBlock), 0, as_stream(stream),
+                     B, V, mode, (long long)ignoreid, logit, ld_logit, target, bt_mask, action, lse, g_ml, g_logp, g_ent, gs_ml, gs_logp, gs_ent, dlogit, ld_dlogit);
+  HAMT_CHECK_LAUNCH("hamt_policy_step_bwd");
+  return HAMT_OK;
+}

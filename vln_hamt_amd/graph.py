@@ -281,10 +281,16 @@ class GraphedTrainStep:
 class GraphedInference:
     """hipGraph capture of a no-grad callable over tensors of fixed shapes (rollout steps of the finetune model: one
     graph per history length for `visual`, one for `history`).  Inputs are copied into static buffers before every replay;
-    the returned tensors are the graph's static outputs (valid until the next call with the same key)."""
+    the returned tensors are the graph's static outputs (valid until the next call with the same key).
 
-    def __init__(self, fn):
+    `state`: tensors `fn` updates IN PLACE (a RolloutRecorder's `ended` / `hist_len` when the step's action choice is part of the
+    captured callable, a HistoryCache's buffer).  The warm-up run in front of a capture really executes, and the first replay follows
+    it: without help the first call with a key would apply such an update twice.  The listed tensors are saved before the warm-up and
+    put back after it, so that every call -- the capturing one included -- applies `fn` exactly once."""
+
+    def __init__(self, fn, state=()):
         self.fn = fn
+        self.state = tuple(state)
         self.graphs = {}
         self.pool = None
         self.stream = streams.role_stream(torch.cuda.current_device(), "capture")
@@ -297,7 +303,10 @@ class GraphedInference:
             cur = torch.cuda.current_stream()
             self.stream.wait_stream(cur)
             with torch.cuda.stream(self.stream):
+                saved = [s_.clone() for s_ in self.state]
                 self.fn(*static)                      # warm-up on the capture stream (allocator, lazy caches)
+                for s_, v in zip(self.state, saved):
+                    s_.copy_(v)
             cur.wait_stream(self.stream)
             torch.cuda.synchronize()
             g = _new_graph()

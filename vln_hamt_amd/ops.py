@@ -1342,5 +1342,75 @@ def a2c_loss(logp, value, reward, mask, last_value=None, entropy=None, gamma=0.9
     return loss, {"policy": parts[0].detach(), "critic": parts[1].detach(), "entropy": parts[2].detach()}
 
 
+POLICY_MODES = {"teacher": 0, "argmax": 1, "sample": 2}      # HAMT_POLICY_*
+
+
+class PolicyStepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, target, bt_mask, cand_len, ended, mask, ob_ang, hist_len, forced_action, uniform, mode, ignoreid, call_id, out):
+        _chk(logit, "policy_step")
+        x = logit.detach()
+        if x.dtype != torch.float32 or x.stride(1) != 1:
+            x = x.to(torch.float32).contiguous()
+        B, V = x.shape
+        dev = x.device
+        A = 0 if ob_ang is None else ob_ang.shape[-1]
+        for name, t_, dt, shape in (("target", target, torch.int64, (B,)), ("bt_mask", bt_mask, torch.uint8, (B, V)), ("cand_len", cand_len, torch.int32, (B,)),
+                                    ("ended", ended, torch.uint8, (B,)), ("mask", mask, torch.float32, (B,)), ("ob_ang", ob_ang, torch.float32, (B, V, A)),
+                                    ("hist_len", hist_len, torch.int32, (B,)), ("forced_action", forced_action, torch.int64, (B,)),
+                                    ("uniform", uniform, torch.float32, (B,))):
+            if t_ is not None and (t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous() or t_.device != dev):
+                raise L.HamtError(f"policy_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+        ml, logp, ent = out if out is not None else (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+        action = torch.empty(B, dtype=torch.int64, device=dev)
+        env_action = torch.empty(B, dtype=torch.int32, device=dev)
+        prev_angle = torch.empty(B, A, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        L.check(L.load().hamt_policy_step_fwd(B, V, A, mode, int(ignoreid), _p(x), x.stride(0), _p(target), _p(bt_mask), _p(cand_len), _p(ended),
+                                              _p(ob_ang), _p(forced_action), _p(uniform), _p(rng_state(dev)), int(call_id), _p(ml), _p(action),
+                                              _p(logp), _p(ent), _p(mask), _p(env_action), _p(prev_angle) if A else None, _p(hist_len), _p(lse),
+                                              _stream()), "hamt_policy_step_fwd")
+        ctx.save_for_backward(x, target, bt_mask, action, lse)
+        ctx.meta = (mode, int(ignoreid))
+        ctx.mark_non_differentiable(action, env_action, prev_angle)
+        ctx.set_materialize_grads(False)       # (no zero-filled gradients for the outputs nobody differentiates: three fill kernels per step)
+        if mode != POLICY_MODES["sample"]:
+            ent = None
+        return ml, logp, ent, action, env_action, prev_angle
+
+    @staticmethod
+    def backward(ctx, g_ml, g_logp, g_ent, *_):
+        x, target, bt_mask, action, lse = ctx.saved_tensors
+        mode, ignoreid = ctx.meta
+        B, V = x.shape
+        def f(g):          # [B] with element stride 1 or 0 (the expanded gradient of a plain sum) goes in as it is: no copy kernel
+            if g is None:
+                return None, 0
+            if g.dtype != torch.float32 or g.stride(0) not in (0, 1):
+                g = g.to(torch.float32).contiguous()
+            return g, g.stride(0)
+        (g_ml, s_ml), (g_logp, s_logp), (g_ent, s_ent) = f(g_ml), f(g_logp), f(g_ent)
+        dx = torch.empty(B, V, dtype=torch.float32, device=x.device)
+        L.check(L.load().hamt_policy_step_bwd(B, V, mode, ignoreid, _p(x), x.stride(0), _p(target), _p(bt_mask), _p(action), _p(lse), _p(g_ml),
+                                              _p(g_logp), _p(g_ent), s_ml, s_logp, s_ent, _p(dx), V, _stream()), "hamt_policy_step_bwd")
+        return (dx,) + (None,) * 13
+
+
+def policy_step(logit, cand_len, ended, mask, mode="sample", target=None, bt_mask=None, ob_ang=None, hist_len=None, forced_action=None,
+                uniform=None, ignoreid=-100, call_id=None, out=None):
+    """The decision and loss side of one rollout step of the finetune agents (finetune_src/r2r/agent_cmt.py:336-401) in one launch,
+    and one more for its backward: `logit` [B, V <= 256] fp32 (-inf at non-candidates) is the only differentiable input.  `mode` is
+    the agent's feedback ('teacher', 'argmax', 'sample'); `target` [B] int64 (`ignoreid` = none), `bt_mask` [B, V] uint8,
+    `cand_len` [B] int32, `ob_ang` [B, V, A] fp32; `forced_action` [B] int64 overrides the choice and `uniform` [B] fp32 the draws
+    of 'sample' (otherwise a counter hash of ops.rng_state, `call_id` and the row).  `ended` [B] uint8, `mask` [B] fp32 and
+    `hist_len` [B] int32 are updated IN PLACE (:447, :418-420, :399-401).  `out` = (ml, logp, ent) [B] fp32 tensors to write into
+    (rows of a recorder's [T, B] arrays) instead of fresh ones.  Returns (ml, logp, ent, action, env_action, prev_angle): the
+    per-row cross-entropy on the unmasked logits, log pi(a_t), the entropy (None unless 'sample'), a_t int64, the environment's
+    action int32 (-1 = stop / ignored / ended) and the chosen candidate's angle feature [B, A].  Nothing in here reads the device
+    from the host; a row whose every slot is masked yields env_action -1 and zero gradients (hamt.h)."""
+    return PolicyStepFn.apply(logit, target, bt_mask, cand_len, ended, mask, ob_ang, hist_len, forced_action, uniform, POLICY_MODES[mode],
+                              ignoreid, next_call_id() if call_id is None else call_id, out)
+
+
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
