@@ -535,6 +535,49 @@ int hamt_policy_step_bwd(int B, int V, int mode, int64_t ignoreid, const float* 
                          const uint8_t* bt_mask, const int64_t* action, const float* lse, const float* g_ml,
                          const float* g_logp, const float* g_ent, int gs_ml, int gs_logp, int gs_ent, float* dlogit, int ld_dlogit,
                          void* stream);
+/* The navigation-graph side of a rollout step and the evaluation metrics (csrc/nav.hip).  The graphs of all scans lie in one arena:
+ * scan s has scan_n[s] nodes and owns the elements [scan_off[s], scan_off[s] + n * n) of `dist` (fp64, all-pairs shortest distances,
+ * dist[x * n + y]) and `nxt` (int32, the next hop from x toward y; nxt[x, x] = x).  Node ids are local to their scan.  Episode b:
+ * ep_scan[b], cur[b] (the node stood on), goal[b] = gt[b][gt_len - 1], gt int32 [B, g_max], path int32 [B, path_cap] (every node
+ * stood on, the start first) with path_len, dtw_row fp64 [B, g_max + 1] (the last row of cal_dtw's matrix for path against gt),
+ * last_dist / last_ndtw fp32 [B] (agent_cmt.py:284-289, :444-445), anomalies int32 [2].  One wave per episode.
+ * g_max above HAMT_NAV_MAX_GT or a path_cap / p_max above HAMT_NAV_MAX_PATH: HAMT_ERR_UNSUPPORTED, nothing launched.
+ *
+ * hamt_nav_observe (before the policy step of step t): target[b] = what agent_cmt.py::_teacher_action returns -- ignoreid if
+ * ended[b]; else the first slot c < cand_len[b] - 1 with cand_node[b, c] == the teacher's viewpoint; else slot cand_len[b] - 1 (STOP)
+ * if that viewpoint is cur[b]; where the reference's assert fails (no teacher viewpoint, or one that is neither): ignoreid and
+ * anomalies[0] += 1.  The teacher's viewpoint (env.py::_teacher_path_action): PATH_STEP gt[t + 1] if t < gt_len - 1 else cur;
+ * PATH_INDEX the successor of cur's first occurrence in gt (cur if it is the last element, none if absent); SHORTEST nxt[cur, goal].
+ * bt_mask[b, c] = 1 where c < cand_len[b] - 1 and cand_node[b, c] is in path[b][:path_len] (:342-349).  cand_node int32 [B, V], -1 =
+ * padding.  target or bt_mask may be NULL (not computed).
+ *
+ * hamt_nav_advance (after it): env_action[b] >= 0 moves episode b to cand_node[b, env_action[b]] and appends it to path; the DTW row
+ * advances by that node alone.  dist = (float)dist[cur, goal], ndtw = (float)exp(-dtw_row[gt_len] / (3 gt_len)); reward_row[b] is
+ * agent_cmt.py:418-441 in fp32 with mask_row[b] = 1 - ended before the step (0: reward 0); a move that leaves the fp32 distance
+ * unchanged (the reference raises NameError) gets ndtw - last_ndtw and anomalies[1] += 1.  last_dist / last_ndtw take dist / ndtw for
+ * every episode.
+ *
+ * hamt_nav_eval: out fp64 [N, HAMT_NAV_EVAL_COLS] = env.py::_eval_item of trajectory i (path [N, p_max], gt [N, g_max], local nodes
+ * of scan[i]) in the column order nav_error, oracle_error, trajectory_steps, trajectory_lengths, success, spl, oracle_success, DTW,
+ * nDTW, SDTW, CLS.  A length outside [1, p_max] / [1, g_max] or a node outside its scan: a row of NaN. */
+#define HAMT_NAV_PATH_STEP 0
+#define HAMT_NAV_PATH_INDEX 1
+#define HAMT_NAV_SHORTEST 2
+#define HAMT_NAV_MAX_GT 512
+#define HAMT_NAV_MAX_PATH 4096
+#define HAMT_NAV_EVAL_COLS 11
+int hamt_nav_observe(int B, int V, int mode, int t, int64_t ignoreid, int g_max, int path_cap, const int32_t* nxt,
+                     const int64_t* scan_off, const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cand_node,
+                     const int32_t* cand_len, const uint8_t* ended, const int32_t* cur, const int32_t* goal, const int32_t* gt,
+                     const int32_t* gt_len, const int32_t* path, const int32_t* path_len, int32_t* anomalies, int64_t* target,
+                     uint8_t* bt_mask, void* stream);
+int hamt_nav_advance(int B, int V, int g_max, int path_cap, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
+                     const int32_t* ep_scan, const int32_t* cand_node, const int32_t* env_action, const float* mask_row,
+                     int32_t* cur, const int32_t* goal, const int32_t* gt, const int32_t* gt_len, int32_t* path, int32_t* path_len,
+                     double* dtw_row, float* last_dist, float* last_ndtw, int32_t* anomalies, float* reward_row, void* stream);
+int hamt_nav_eval(int N, int p_max, int g_max, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
+                  const int32_t* scan, const int32_t* path, const int32_t* path_len, const int32_t* gt, const int32_t* gt_len,
+                  double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

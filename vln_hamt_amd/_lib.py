@@ -159,6 +159,9 @@ SIGNATURES = {
     "hamt_a2c_bwd": [i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp],
     "hamt_policy_step_fwd": [i32, i32, i32, i32, C.c_int64, vp, i32] + [vp] * 8 + [u32] + [vp] * 10,
     "hamt_policy_step_bwd": [i32, i32, i32, C.c_int64, vp, i32] + [vp] * 7 + [i32, i32, i32, vp, i32, vp],
+    "hamt_nav_observe": [i32, i32, i32, i32, C.c_int64, i32, i32] + [vp] * 17,
+    "hamt_nav_advance": [i32, i32, i32, i32] + [vp] * 19,
+    "hamt_nav_eval": [i32, i32, i32] + [vp] * 10,
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

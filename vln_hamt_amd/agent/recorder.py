@@ -6,7 +6,11 @@ blocking `.cpu()`, two Python loops over the batch and an upload, and keeps per-
 (:476-522).  Here one step is `ops.policy_step` (one launch, one more for its backward) writing straight into row t of the [T_max, B]
 arrays `ops.a2c_loss` reads, and the only thing that crosses to the host is the int32 environment action the simulator needs.
 
-What stays on the host: the teacher action lookup (`_teacher_action`), the reward shaping (:407-445), the simulator.
+With `nav=` (agent.NavEpisodes: the episodes' place in the navigation graph, on the device) the step is `ops.nav_observe` -> `ops.policy_step`
+-> `ops.nav_advance`: the teacher action lookup (`_teacher_action`, :199-211), the back-track mask (:342-349) and the reward shaping
+(:407-445) run on the device too, and the reward lands in row t of `reward`.
+
+What stays on the host: the simulator (and, without `nav=`, the teacher action lookup and the reward shaping, handed in by the caller).
 """
 from __future__ import annotations
 
@@ -48,6 +52,9 @@ class RolloutRecorder:
         rec.set_rewards(rewards)
         loss, logs = rec.loss(critic, hidden_states, last_h, train_ml=0.2)
 
+    With the navigation graph on the device (`nav = NavEpisodes(graphs, T, B).reset(scans, starts, gt_paths)`), target, bt_mask and the
+    rewards need no host: `rec.step(t, logit, cand_lens=..., nav=nav, cand_nodes=cand_nodes, teacher_mode='path_step')`, no `set_rewards`.
+
     Draws of 'sample': step t hashes (ops.rng_state's seed and epoch, a call id, the row).  `reset()` takes a FRESH block of T_max call
     ids from ops.next_call_id, as every dropout call does, so rollouts drawn eagerly differ from each other whether or not anything
     advances the epoch.  A captured step has its call id baked into the graph: it draws afresh on a replay only when the epoch has
@@ -77,7 +84,7 @@ class RolloutRecorder:
         self.env_host_np = self.env_host.numpy()
         self._event = torch.cuda.Event()
         self._rows = {"ml": [], "logp": [], "ent": []}
-        self.feedback = None
+        self.feedback = self.target = self.bt_mask = None
 
     def reset(self, batch_size=None, fresh_draws=True):
         """New rollout: nothing ended, history length 1 (the global [CLS] embedding, agent_cmt.py:305-306), no steps recorded, and
@@ -100,12 +107,16 @@ class RolloutRecorder:
         return len(self._rows["ml"])
 
     def step(self, t, logit, target=None, cand_lens=None, bt_mask=None, ob_ang_feats=None, feedback="sample", forced_action=None,
-             uniform=None, sync=True):
+             uniform=None, sync=True, nav=None, cand_nodes=None, teacher_mode="path_step"):
         """Step t of the rollout on `logit` [B, V].  Returns (a_t, env_action, prev_act_angle): a_t int64 [B] on the device, the
         environment's action (int32, -1 = stop / ignored / ended) as a numpy view of the pinned host buffer -- the step's ONE
         device-to-host copy, followed by one event wait -- and the chosen candidate's angle feature [B, A] for `history`.
         sync=False returns the device tensor instead and copies nothing (the form used inside a captured graph).
-        `cand_lens` is an int32 device tensor [B] (a host list is uploaded)."""
+        `cand_lens` is an int32 device tensor [B] (a host list is uploaded).
+        `nav` (a NavEpisodes) with `cand_nodes` int32 [B, V] (each navigable candidate's node, -1 = padding): `target` and `bt_mask` left
+        at None come from `ops.nav_observe` (`teacher_mode`: 'path_step', 'path_index' or 'shortest', env.py::_teacher_path_action;
+        False = none, as a run without imitation loss / without the back-track mask), and `ops.nav_advance` moves the episodes and
+        writes the step's reward into row t of `reward`."""
         if t > self.steps or t >= self.T_max:
             raise ops.L.HamtError(f"RolloutRecorder.step: step {t} after {self.steps} recorded steps (T_max {self.T_max})")
         for rows in self._rows.values():         # (a step recorded again -- the warm-up and the capture of a graphed step -- replaces its row)
@@ -113,6 +124,14 @@ class RolloutRecorder:
         if not torch.is_tensor(cand_lens):
             cand_lens = torch.as_tensor(np.asarray(cand_lens, dtype=np.int32)).to(self.device, non_blocking=True)
         B = self.B
+        if nav is not None:
+            if cand_nodes is None:
+                raise ops.L.HamtError("RolloutRecorder.step: nav= needs cand_nodes (int32 [B, V], the node of every navigable candidate)")
+            tgt, btm = ops.nav_observe(nav, t, cand_nodes, cand_lens, self.ended, mode=teacher_mode, ignoreid=self.ignoreid,
+                                       target=target is None, bt_mask=bt_mask is None)
+            target, bt_mask = (tgt if target is None else target), (btm if bt_mask is None else bt_mask)
+        target, bt_mask = (None if target is False else target), (None if bt_mask is False else bt_mask)
+        self.target, self.bt_mask = target, bt_mask          # (what this step used: device tensors, for the caller's logs)
         out = tuple(_alias(b_, t * B, (B,)) for b_ in (self.ml, self.logp, self.ent))
         ml, logp, ent, a_t, env_action, prev_angle = ops.policy_step(
             logit, cand_lens, self.ended, _alias(self.mask, t * B, (B,)), mode=feedback, target=target, bt_mask=bt_mask, ob_ang=ob_ang_feats,
@@ -122,6 +141,8 @@ class RolloutRecorder:
         self._rows["logp"].append(logp)
         self._rows["ent"].append(ent)
         self.feedback = feedback
+        if nav is not None:
+            ops.nav_advance(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
         if not sync:
             return a_t, env_action, prev_angle
         return a_t, self.to_host(env_action), prev_angle

@@ -1412,5 +1412,67 @@ def policy_step(logit, cand_len, ended, mask, mode="sample", target=None, bt_mas
                               ignoreid, next_call_id() if call_id is None else call_id, out)
 
 
+NAV_TEACHER_MODES = {"path_step": 0, "path_index": 1, "shortest": 2}      # HAMT_NAV_*
+NAV_EVAL_COLS = ("nav_error", "oracle_error", "trajectory_steps", "trajectory_lengths", "success", "spl", "oracle_success", "DTW", "nDTW",
+                 "SDTW", "CLS")
+
+
+def _nav_arg(name, t_, dt, shape, dev):
+    if t_.dtype != dt or tuple(t_.shape) != tuple(shape) or not t_.is_contiguous() or t_.device != dev:
+        raise L.HamtError(f"{name} must be a contiguous {dt} tensor of shape {tuple(shape)} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+    return t_
+
+
+def nav_observe(ep, t, cand_node, cand_len, ended, mode="path_step", ignoreid=-100, target=True, bt_mask=True):
+    """Before the policy step of step `t`, one launch for the B episodes of `ep` (agent.NavEpisodes): the teacher's slot
+    (agent_cmt.py::_teacher_action over env.py::_teacher_path_action, `mode` in NAV_TEACHER_MODES) and the back-track mask (:342-349)
+    from `cand_node` int32 [B, V] (the local node of each navigable candidate, -1 = padding), `cand_len` int32 [B] (STOP slot counted)
+    and `ended` uint8 [B].  Returns (target int64 [B] or None, bt_mask uint8 [B, V] or None); nothing is read from the host."""
+    _chk(cand_node, "nav_observe")
+    dev, (B, V), g = cand_node.device, cand_node.shape, ep.graphs
+    _nav_arg("nav_observe: cand_node", cand_node, torch.int32, (ep.B, V), dev)
+    _nav_arg("nav_observe: cand_len", cand_len, torch.int32, (B,), dev)
+    _nav_arg("nav_observe: ended", ended, torch.uint8, (B,), dev)
+    tgt = torch.empty(B, dtype=torch.int64, device=dev) if target else None
+    btm = torch.empty(B, V, dtype=torch.uint8, device=dev) if bt_mask else None
+    L.check(L.load().hamt_nav_observe(B, V, NAV_TEACHER_MODES[mode], int(t), int(ignoreid), ep.G_max, ep.path_cap, _p(g.nxt), _p(g.scan_offset),
+                                      _p(g.scan_n), _p(ep.scan), _p(cand_node), _p(cand_len), _p(ended), _p(ep.cur), _p(ep.goal), _p(ep.gt),
+                                      _p(ep.gt_len), _p(ep.path), _p(ep.path_len), _p(ep.anomalies), _p(tgt), _p(btm), _stream()), "hamt_nav_observe")
+    return tgt, btm
+
+
+def nav_advance(ep, cand_node, env_action, mask, reward):
+    """After the policy step, one launch: `env_action` int32 [B] (-1 = stop / ignored / ended) moves the episodes of `ep` IN PLACE
+    (current node, path, DTW row, last_dist / last_ndtw), and the shaped reward of the step (agent_cmt.py:407-445; `mask` fp32 [B] =
+    1 - ended before the step) is written into `reward` fp32 [B] (row t of a recorder's array)."""
+    _chk(cand_node, "nav_advance")
+    dev, (B, V), g = cand_node.device, cand_node.shape, ep.graphs
+    _nav_arg("nav_advance: cand_node", cand_node, torch.int32, (ep.B, V), dev)
+    _nav_arg("nav_advance: env_action", env_action, torch.int32, (B,), dev)
+    _nav_arg("nav_advance: mask", mask, torch.float32, (B,), dev)
+    _nav_arg("nav_advance: reward", reward, torch.float32, (B,), dev)
+    L.check(L.load().hamt_nav_advance(B, V, ep.G_max, ep.path_cap, _p(g.dist), _p(g.scan_offset), _p(g.scan_n), _p(ep.scan), _p(cand_node),
+                                      _p(env_action), _p(mask), _p(ep.cur), _p(ep.goal), _p(ep.gt), _p(ep.gt_len), _p(ep.path), _p(ep.path_len),
+                                      _p(ep.dtw_row), _p(ep.last_dist), _p(ep.last_ndtw), _p(ep.anomalies), _p(reward), _stream()), "hamt_nav_advance")
+    return reward
+
+
+def nav_eval(graphs, scan, path, path_len, gt, gt_len):
+    """env.py::_eval_item for N finished trajectories in one launch: `scan` int32 [N] (index into `graphs`, an agent.NavGraphs on the
+    device), `path` int32 [N, P_max] / `gt` int32 [N, G_max] of local node ids with their lengths.  Returns fp64 [N, 11] in the column
+    order NAV_EVAL_COLS."""
+    _chk(path, "nav_eval")
+    dev, (N, P), G = path.device, path.shape, gt.shape[1]
+    _nav_arg("nav_eval: scan", scan, torch.int32, (N,), dev)
+    _nav_arg("nav_eval: path", path, torch.int32, (N, P), dev)
+    _nav_arg("nav_eval: path_len", path_len, torch.int32, (N,), dev)
+    _nav_arg("nav_eval: gt", gt, torch.int32, (N, G), dev)
+    _nav_arg("nav_eval: gt_len", gt_len, torch.int32, (N,), dev)
+    out = torch.empty(N, len(NAV_EVAL_COLS), dtype=torch.float64, device=dev)
+    L.check(L.load().hamt_nav_eval(N, P, G, _p(graphs.dist), _p(graphs.scan_offset), _p(graphs.scan_n), _p(scan), _p(path), _p(path_len), _p(gt),
+                                   _p(gt_len), _p(out), _stream()), "hamt_nav_eval")
+    return out
+
+
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
