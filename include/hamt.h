@@ -578,6 +578,54 @@ int hamt_nav_advance(int B, int V, int g_max, int path_cap, const double* dist, 
 int hamt_nav_eval(int N, int p_max, int g_max, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
                   const int32_t* scan, const int32_t* path, const int32_t* path_len, const int32_t* gt, const int32_t* gt_len,
                   double* out, void* stream);
+/* The same for the reference's other three agents (csrc/nav.hip, the same arena, the same clamping and NaN rows).
+ *
+ * Goal sets (CVDN's end_panos, REVERIE's viewpoints an object is visible from): goals int32 [B, e_max] with goal_len [B]; the distance
+ * of a node is the minimum over the set, taken in fp64.  e_max above HAMT_NAV_MAX_GOALS: HAMT_ERR_UNSUPPORTED, nothing launched.
+ * hamt_nav_advance_goals (after the policy step): the move as hamt_nav_advance (new node, appended to path);
+ * dist = (float)min_e dist[cur, goals[e]], 0 for an empty set (cvdn/env.py:85-86); reward_row[b] is cvdn/agent.py:174-203 =
+ * reverie/agent.py:337-366: 0 where mask_row[b] == 0 (ended before the step); a stop (env_action < 0) 2 if dist == 0 else -2; a move
+ * +1, -1 or 0 by the sign of -(dist - last_dist) (an unchanged distance is no anomaly here).  last_dist takes dist for every episode.
+ * There is no DTW row and no last_ndtw.
+ * hamt_nav_eval_goals: out fp64 [N, HAMT_NAV_GOALS_EVAL_COLS] in the column order trajectory_steps, trajectory_lengths, success,
+ * oracle_success, spl, gp, spl_ratio.  gt_lengths = the sum of dist along gt (reverie/env.py::_eval_item) or, with gt and gt_len NULL,
+ * min_e dist[path[0], goals[e]] (cvdn/env.py::_eval_item); success = path[-1] in goals, oracle_success = any node of path in goals;
+ * spl_ratio = gt_lengths / max(trajectory_lengths, gt_lengths, 0.01), spl = success * spl_ratio (REVERIE's rgspl = rgs * spl_ratio is
+ * formed by the caller); gp = gt_lengths - min_e dist[path[-1], goals[e]].  A length outside [1, p_max] / [1, e_max] / [1, g_max] or a
+ * node outside its scan: a row of NaN.  Only lengths are taken along gt, so g_max may reach HAMT_NAV_MAX_PATH.
+ *
+ * Return trips (R2R-Back: to the mid-stop, then on to the path's end): midstop int32 [B] (the ground truth's), first_ended uint8 [B]
+ * (the first STOP has been made), midstop_at int32 [B] (where, -1 = not yet), and the recorder's `ended` uint8 [B].
+ * hamt_nav_advance_back runs after the policy step, which has set ended |= stop: the move, the DTW row and ndtw as hamt_nav_advance;
+ * d0 = (float)dist[cur, midstop], d1 = (float)dist[cur, goal], dist = first_ended (before the step) ? d1 : d0; reward_row[b] is the
+ * block of hamt_nav_advance (agent_r2rback.py:241-265) on this dist, an unchanged fp32 distance on a move counted in anomalies[1].  An
+ * episode with mask_row[b] != 0 that stops with first_ended clear: midstop_at = cur, first_ended = 1, last_dist = d1, and
+ * ended = (end_on_miss && !(dist < 3)) -- the reference ends a missed mid-stop only under RL training (:252), otherwise the episode
+ * goes on (:275).  Every other episode: last_dist = dist, `ended` as the policy step left it; one with mask_row[b] == 0 gets
+ * first_ended = 1 (:276).  last_ndtw takes ndtw for every episode.
+ * hamt_nav_eval_back: out fp64 [N, HAMT_NAV_BACK_EVAL_COLS] = env.py::R2RBackBatch._eval_item in the column order nav_error,
+ * trajectory_steps, trajectory_lengths, success, spl, DTW, nDTW, SDTW, CLS; midstop[i] = -1 for None; success = midstop >= 0 and
+ * dist[midstop, gt_midstop] <= 3 and dist[path[-1], gt[-1]] <= 3.  NaN rows as hamt_nav_eval, also for a midstop outside [-1, n) or
+ * a gt_midstop outside [0, n). */
+#define HAMT_NAV_MAX_GOALS 256
+#define HAMT_NAV_GOALS_EVAL_COLS 7
+#define HAMT_NAV_BACK_EVAL_COLS 9
+int hamt_nav_advance_goals(int B, int V, int e_max, int path_cap, const double* dist, const int64_t* scan_off,
+                           const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cand_node, const int32_t* env_action,
+                           const float* mask_row, int32_t* cur, const int32_t* goals, const int32_t* goal_len, int32_t* path,
+                           int32_t* path_len, float* last_dist, float* reward_row, void* stream);
+int hamt_nav_advance_back(int B, int V, int g_max, int path_cap, int end_on_miss, const double* dist, const int64_t* scan_off,
+                          const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cand_node, const int32_t* env_action,
+                          const float* mask_row, int32_t* cur, const int32_t* goal, const int32_t* midstop, const int32_t* gt,
+                          const int32_t* gt_len, int32_t* path, int32_t* path_len, double* dtw_row, float* last_dist,
+                          float* last_ndtw, uint8_t* first_ended, int32_t* midstop_at, uint8_t* ended, int32_t* anomalies,
+                          float* reward_row, void* stream);
+int hamt_nav_eval_goals(int N, int p_max, int e_max, int g_max, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
+                        const int32_t* scan, const int32_t* path, const int32_t* path_len, const int32_t* goals,
+                        const int32_t* goal_len, const int32_t* gt, const int32_t* gt_len, double* out, void* stream);
+int hamt_nav_eval_back(int N, int p_max, int g_max, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
+                       const int32_t* scan, const int32_t* path, const int32_t* path_len, const int32_t* gt, const int32_t* gt_len,
+                       const int32_t* midstop, const int32_t* gt_midstop, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

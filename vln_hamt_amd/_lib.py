@@ -162,6 +162,10 @@ SIGNATURES = {
     "hamt_nav_observe": [i32, i32, i32, i32, C.c_int64, i32, i32] + [vp] * 17,
     "hamt_nav_advance": [i32, i32, i32, i32] + [vp] * 19,
     "hamt_nav_eval": [i32, i32, i32] + [vp] * 10,
+    "hamt_nav_advance_goals": [i32, i32, i32, i32] + [vp] * 15,
+    "hamt_nav_advance_back": [i32, i32, i32, i32, i32] + [vp] * 23,
+    "hamt_nav_eval_goals": [i32, i32, i32, i32] + [vp] * 12,
+    "hamt_nav_eval_back": [i32, i32, i32] + [vp] * 12,
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

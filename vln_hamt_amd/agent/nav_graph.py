@@ -8,6 +8,10 @@ Together with `ops.nav_observe` they replace the reference agent's host loops ar
 `NavGraphs.eval_metrics` replaces env.py::eval_metrics / `_eval_item`.  In the Matterport graph a move is deterministic (the new
 viewpoint is the chosen candidate's), so none of this needs the simulator.
 
+`GoalSetEpisodes` (CVDN, REVERIE: the goal is a set of viewpoints) and `ReturnEpisodes` (R2R-Back: to a mid-stop, then on to the path's
+end) are the same state with a few more fields, advanced by `ops.nav_advance_goals` / `ops.nav_advance_back`;
+`NavGraphs.eval_metrics_cvdn` / `eval_metrics_reverie` / `eval_metrics_back` replace those environments' `eval_metrics`.
+
 The tables and all arithmetic on them stay fp64: the fp32 `dist` the agent sees is one rounding of the same double the reference rounds.
 """
 from __future__ import annotations
@@ -23,6 +27,7 @@ from .. import ops
 from ..data.r2r_data import load_nav_graphs
 
 MAX_GT, MAX_PATH = 512, 4096            # HAMT_NAV_MAX_GT / HAMT_NAV_MAX_PATH
+MAX_GOALS = 256                         # HAMT_NAV_MAX_GOALS
 
 
 def _next_hop(w, dist):
@@ -121,6 +126,83 @@ class NavGraphs:
                        "spl": mean("spl") * 100, "nDTW": mean("nDTW") * 100, "SDTW": mean("SDTW") * 100, "CLS": mean("CLS") * 100}
         return avg_metrics, metrics
 
+    def _up(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device, non_blocking=True)
+
+    @staticmethod
+    def _metric_lists(out, cols):
+        metrics = defaultdict(list)
+        for c, k in enumerate(cols):
+            metrics[k] = out[:, c].astype(np.int64).tolist() if k == "trajectory_steps" else out[:, c].tolist()
+        return metrics
+
+    def eval_goal_items(self, scans, paths, goal_sets, gt_paths=None):
+        """cvdn/env.py::_eval_item (no `gt_paths`) or the navigation part of reverie/env.py::_eval_item of N trajectories in one launch:
+        fp64 [N, 7] on the device, columns ops.NAV_GOALS_EVAL_COLS.  A goal set is taken as a set: duplicates drop out."""
+        sets = [list(dict.fromkeys(g)) for g in goal_sets]
+        sc, pa, pl = self.pack(scans, paths)
+        _, go, gl = self.pack(scans, sets)
+        gt = gtl = None
+        if gt_paths is not None:
+            for p, g in zip(paths, gt_paths):
+                assert g[0] == p[0], "Result trajectories should include the start position"
+            _, gt, gtl = self.pack(scans, gt_paths)
+            gt, gtl = self._up(gt), self._up(gtl)
+        return ops.nav_eval_goals(self, self._up(sc), self._up(pa), self._up(pl), self._up(go), self._up(gl), gt, gtl)
+
+    def eval_metrics_cvdn(self, preds, gt_trajs):
+        """cvdn/env.py::eval_metrics: `gt_trajs` = {instr_id: (scan, end_panos)}.  Returns the reference's (avg_metrics, metrics)."""
+        ids = [item["instr_id"] for item in preds]
+        scans = [gt_trajs[i][0] for i in ids]
+        out = self.eval_goal_items(scans, [[x[0] for x in item["trajectory"]] for item in preds], [gt_trajs[i][1] for i in ids]).cpu().numpy()
+        metrics = self._metric_lists(out[:, :6], ops.NAV_GOALS_EVAL_COLS[:6])
+        metrics["instr_id"] = ids
+        mean = lambda k: np.mean(metrics[k])
+        avg_metrics = {"steps": mean("trajectory_steps"), "lengths": mean("trajectory_lengths"), "sr": mean("success") * 100,
+                       "oracle_sr": mean("oracle_success") * 100, "spl": mean("spl") * 100, "gp": mean("gp")}
+        return avg_metrics, metrics
+
+    def eval_metrics_reverie(self, preds, gt_trajs, obj2viewpoint):
+        """reverie/env.py::ReverieNavRefBatch.eval_metrics: `preds` items carry 'predObjId', `gt_trajs` = {instr_id: (scan, path, objId)},
+        `obj2viewpoint` = {'scan_objid': [viewpoints the object is visible from]}.  `rgs` compares object ids on the host; `rgspl` is
+        rgs times the device's spl_ratio."""
+        ids = [item["instr_id"] for item in preds]
+        scans = [gt_trajs[i][0] for i in ids]
+        goal_sets = [obj2viewpoint["%s_%s" % (gt_trajs[i][0], str(gt_trajs[i][2]))] for i in ids]
+        for i, g in zip(ids, goal_sets):
+            assert len(g) > 0, "%s_%s" % (gt_trajs[i][0], str(gt_trajs[i][2]))
+        out = self.eval_goal_items(scans, [[x[0] for x in item["trajectory"]] for item in preds], goal_sets, [gt_trajs[i][1] for i in ids]).cpu().numpy()
+        metrics = self._metric_lists(out[:, :5], ops.NAV_GOALS_EVAL_COLS[:5])
+        metrics["rgs"] = [float(str(item["predObjId"]) == str(gt_trajs[i][2])) for item, i in zip(preds, ids)]
+        metrics["rgspl"] = (np.asarray(metrics["rgs"]) * out[:, 6]).tolist()
+        metrics["instr_id"] = ids
+        mean = lambda k: np.mean(metrics[k])
+        avg_metrics = {"steps": mean("trajectory_steps"), "lengths": mean("trajectory_lengths"), "sr": mean("success") * 100,
+                       "oracle_sr": mean("oracle_success") * 100, "spl": mean("spl") * 100, "rgs": mean("rgs") * 100, "rgspl": mean("rgspl") * 100}
+        return avg_metrics, metrics
+
+    def eval_metrics_back(self, preds, gt_trajs, gt_midstops):
+        """env.py::R2RBackBatch.eval_metrics: `preds` items carry 'midstop' (a viewpoint or None), `gt_trajs` = {instr_id: (scan, path)},
+        `gt_midstops` = {instr_id: viewpoint}."""
+        ids = [item["instr_id"] for item in preds]
+        scans = [gt_trajs[i][0] for i in ids]
+        paths, gts = [[x[0] for x in item["trajectory"]] for item in preds], [gt_trajs[i][1] for i in ids]
+        for p, g in zip(paths, gts):
+            assert g[0] == p[0], "Result trajectories should include the start position"
+        sc, pa, pl = self.pack(scans, paths)
+        _, gt, gl = self.pack(scans, gts)
+        mid = np.array([-1 if item["midstop"] is None else self.node_id(s, item["midstop"]) for s, item in zip(scans, preds)], np.int32)
+        gmid = np.array([self.node_id(s, gt_midstops[i]) for s, i in zip(scans, ids)], np.int32)
+        out = ops.nav_eval_back(self, self._up(sc), self._up(pa), self._up(pl), self._up(gt), self._up(gl), self._up(mid), self._up(gmid)).cpu().numpy()
+        metrics = self._metric_lists(out, ops.NAV_BACK_EVAL_COLS)
+        metrics["success"] = out[:, 3].astype(np.int64).tolist()           # (an int in the reference)
+        metrics["instr_id"] = ids
+        mean = lambda k: np.mean(metrics[k])
+        avg_metrics = {"steps": mean("trajectory_steps"), "lengths": mean("trajectory_lengths"), "nav_error": mean("nav_error"),
+                       "sr": mean("success") * 100, "spl": mean("spl") * 100, "nDTW": mean("nDTW") * 100, "SDTW": mean("SDTW") * 100,
+                       "CLS": mean("CLS") * 100}
+        return avg_metrics, metrics
+
 
 class NavEpisodes:
     """The B episodes of one rollout over `graphs` (on the device).  One uint8 arena holds every field, so `reset` is one upload from
@@ -134,16 +216,20 @@ class NavEpisodes:
               ("anomalies", np.int32, "2"), ("gt", np.int32, "BG"), ("path", np.int32, "BP"), ("last_dist", np.float32, "B"),
               ("last_ndtw", np.float32, "B"), ("dtw_row", np.float64, "BR"))
     MUTATED = ("cur", "path", "path_len", "dtw_row", "last_dist", "last_ndtw", "anomalies")
+    KIND = "r2r"                        # which advance launch RolloutRecorder.step makes
 
-    def __init__(self, graphs: NavGraphs, max_steps: int, batch_size: int, max_gt: int = 64):
+    def __init__(self, graphs: NavGraphs, max_steps: int, batch_size: int, max_gt: int = 64, max_goals: int = 1):
         if graphs.device is None:
             raise ops.L.HamtError("NavEpisodes: the graphs are not on a device (NavGraphs(dir, device=...)); there is no CPU path")
         self.graphs, self.T_max, self.B, self.G_max = graphs, int(max_steps), int(batch_size), int(max_gt)
         self.path_cap = self.T_max + 1
         if not 0 < self.G_max <= MAX_GT or self.path_cap > MAX_PATH:
             raise ops.L.HamtError(f"NavEpisodes: max_gt {self.G_max} / max_steps {self.T_max} outside the supported (0, {MAX_GT}] / [0, {MAX_PATH})")
+        self.E_max = int(max_goals)
+        if not 0 < self.E_max <= MAX_GOALS:
+            raise ops.L.HamtError(f"NavEpisodes: max_goals {self.E_max} outside the supported (0, {MAX_GOALS}]")
         B = self.B
-        dims = {"B": (B,), "2": (2,), "BG": (B, self.G_max), "BP": (B, self.path_cap), "BR": (B, self.G_max + 1)}
+        dims = {"B": (B,), "2": (2,), "BG": (B, self.G_max), "BP": (B, self.path_cap), "BR": (B, self.G_max + 1), "BE": (B, self.E_max)}
         layout, off = [], 0
         for name, dt, d in self.FIELDS:
             nbytes = int(np.prod(dims[d])) * np.dtype(dt).itemsize
@@ -160,6 +246,10 @@ class NavEpisodes:
 
     def reset(self, scans, start_viewpoints, gt_paths):
         """New rollout: episode b stands on start_viewpoints[b] of scans[b] and is scored against gt_paths[b] (viewpoint names)."""
+        self._fill(scans, start_viewpoints, gt_paths)
+        return self._upload()
+
+    def _fill(self, scans, start_viewpoints, gt_paths):
         g, h = self.graphs, self._np
         assert len(scans) == len(start_viewpoints) == len(gt_paths) == self.B, (len(scans), self.B)
         if max(len(p) for p in gt_paths) > self.G_max or min(len(p) for p in gt_paths) < 1:
@@ -178,6 +268,8 @@ class NavEpisodes:
             h["dtw_row"][b, 1:G + 1] = np.cumsum(dist[start, gt])          # (cal_dtw's first row: only `left` is finite)
             h["last_dist"][b] = dist[start, gt[-1]]
             h["last_ndtw"][b] = np.exp(-h["dtw_row"][b, G] / (3.0 * G))
+
+    def _upload(self):
         self.arena.copy_(self._host, non_blocking=True)
         self._event.record()
         return self
@@ -185,3 +277,57 @@ class NavEpisodes:
     def state_tensors(self):
         """everything a step mutates (graph.GraphedInference's `state`)"""
         return tuple(getattr(self, k) for k in self.MUTATED)
+
+
+class GoalSetEpisodes(NavEpisodes):
+    """Episodes whose goal is a SET of viewpoints (CVDN's `end_panos`, REVERIE's viewpoints the object is visible from): NavEpisodes'
+    fields, then goals int32 [B, E_max] and goal_len int32 [B].  `last_dist` is the fp32 minimum over the set (cvdn/agent.py:52-55), 0
+    for an empty set; there is no nDTW term, so `dtw_row` / `last_ndtw` only keep their initial values.  Advanced by
+    `ops.nav_advance_goals`.  `max_goals` <= 256 (HAMT_NAV_MAX_GOALS)."""
+
+    FIELDS = NavEpisodes.FIELDS + (("goals", np.int32, "BE"), ("goal_len", np.int32, "B"))
+    MUTATED = ("cur", "path", "path_len", "last_dist", "anomalies")
+    KIND = "goals"
+
+    def __init__(self, graphs: NavGraphs, max_steps: int, batch_size: int, max_gt: int = 64, max_goals: int = 64):
+        super().__init__(graphs, max_steps, batch_size, max_gt=max_gt, max_goals=max_goals)
+
+    def reset(self, scans, start_viewpoints, gt_paths, goal_sets):
+        """`gt_paths[b]` feeds the teacher of `ops.nav_observe` (the host picks it: the shortest path to a drawn end_pano, or the player's
+        path); `goal_sets[b]` is the list of goal viewpoints, possibly empty, duplicates allowed."""
+        assert len(goal_sets) == self.B, (len(goal_sets), self.B)
+        if max((len(e) for e in goal_sets), default=0) > self.E_max:
+            raise ops.L.HamtError(f"GoalSetEpisodes.reset: a goal set larger than max_goals = {self.E_max}")
+        self._fill(scans, start_viewpoints, gt_paths)
+        g, h = self.graphs, self._np
+        _, h["goals"][:], h["goal_len"][:] = g.pack(scans, goal_sets, self.E_max)
+        for b, scan in enumerate(scans):
+            E = int(h["goal_len"][b])
+            h["last_dist"][b] = g.dist_host[scan][h["cur"][b], h["goals"][b, :E]].min() if E else 0.0
+        return self._upload()
+
+
+class ReturnEpisodes(NavEpisodes):
+    """Return trips (R2R-Back): the ground-truth path leads to `midstop` and on to its end.  NavEpisodes' fields, then midstop int32 [B]
+    (the ground truth's), midstop_at int32 [B] (where the agent made its first STOP, -1 = not yet) and first_ended uint8 [B].
+    `last_dist` starts as the distance to the mid-stop (agent_r2rback.py:106-107).  Advanced by `ops.nav_advance_back`."""
+
+    FIELDS = NavEpisodes.FIELDS + (("midstop", np.int32, "B"), ("midstop_at", np.int32, "B"), ("first_ended", np.uint8, "B"))
+    MUTATED = NavEpisodes.MUTATED + ("first_ended", "midstop_at")
+    KIND = "back"
+
+    def reset(self, scans, start_viewpoints, gt_paths, midstops):
+        assert len(midstops) == self.B, (len(midstops), self.B)
+        self._fill(scans, start_viewpoints, gt_paths)
+        g, h = self.graphs, self._np
+        h["midstop_at"][:] = -1
+        h["first_ended"][:] = 0
+        for b, (scan, vp) in enumerate(zip(scans, midstops)):
+            h["midstop"][b] = g.node_id(scan, vp)
+            h["last_dist"][b] = g.dist_host[scan][h["cur"][b], h["midstop"][b]]
+        self._scans = list(scans)
+        return self._upload()
+
+    def midstops(self):
+        """traj['midstop'] of every episode: the viewpoint of its first STOP, or None (one blocking read of midstop_at)"""
+        return [None if v < 0 else self.graphs.viewpoint(s, v) for s, v in zip(self._scans, self.midstop_at.cpu().tolist())]

@@ -7,7 +7,8 @@ blocking `.cpu()`, two Python loops over the batch and an upload, and keeps per-
 arrays `ops.a2c_loss` reads, and the only thing that crosses to the host is the int32 environment action the simulator needs.
 
 With `nav=` (agent.NavEpisodes: the episodes' place in the navigation graph, on the device) the step is `ops.nav_observe` -> `ops.policy_step`
--> `ops.nav_advance`: the teacher action lookup (`_teacher_action`, :199-211), the back-track mask (:342-349) and the reward shaping
+-> `ops.nav_advance` (`ops.nav_advance_goals` for CVDN's / REVERIE's goal sets, `ops.nav_advance_back` for R2R-Back's return trips): the
+teacher action lookup (`_teacher_action`, :199-211), the back-track mask (:342-349) and the reward shaping
 (:407-445) run on the device too, and the reward lands in row t of `reward`.
 
 What stays on the host: the simulator (and, without `nav=`, the teacher action lookup and the reward shaping, handed in by the caller).
@@ -107,7 +108,7 @@ class RolloutRecorder:
         return len(self._rows["ml"])
 
     def step(self, t, logit, target=None, cand_lens=None, bt_mask=None, ob_ang_feats=None, feedback="sample", forced_action=None,
-             uniform=None, sync=True, nav=None, cand_nodes=None, teacher_mode="path_step"):
+             uniform=None, sync=True, nav=None, cand_nodes=None, teacher_mode="path_step", end_on_miss=None):
         """Step t of the rollout on `logit` [B, V].  Returns (a_t, env_action, prev_act_angle): a_t int64 [B] on the device, the
         environment's action (int32, -1 = stop / ignored / ended) as a numpy view of the pinned host buffer -- the step's ONE
         device-to-host copy, followed by one event wait -- and the chosen candidate's angle feature [B, A] for `history`.
@@ -116,7 +117,10 @@ class RolloutRecorder:
         `nav` (a NavEpisodes) with `cand_nodes` int32 [B, V] (each navigable candidate's node, -1 = padding): `target` and `bt_mask` left
         at None come from `ops.nav_observe` (`teacher_mode`: 'path_step', 'path_index' or 'shortest', env.py::_teacher_path_action;
         False = none, as a run without imitation loss / without the back-track mask), and `ops.nav_advance` moves the episodes and
-        writes the step's reward into row t of `reward`."""
+        writes the step's reward into row t of `reward`.  The episodes' kind picks that launch: a GoalSetEpisodes (CVDN, REVERIE) takes
+        `ops.nav_advance_goals`; a ReturnEpisodes (R2R-Back) takes `ops.nav_advance_back`, which also reads and writes `ended` (the first
+        STOP does not end a return trip) -- `end_on_miss` (a missed mid-stop ends the episode, agent_r2rback.py:252, which sits under
+        `if train_rl:`) defaults to feedback == 'sample'."""
         if t > self.steps or t >= self.T_max:
             raise ops.L.HamtError(f"RolloutRecorder.step: step {t} after {self.steps} recorded steps (T_max {self.T_max})")
         for rows in self._rows.values():         # (a step recorded again -- the warm-up and the capture of a graphed step -- replaces its row)
@@ -142,7 +146,14 @@ class RolloutRecorder:
         self._rows["ent"].append(ent)
         self.feedback = feedback
         if nav is not None:
-            ops.nav_advance(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
+            kind = getattr(nav, "KIND", "r2r")
+            if kind == "r2r":
+                ops.nav_advance(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
+            elif kind == "goals":
+                ops.nav_advance_goals(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
+            else:
+                ops.nav_advance_back(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)), self.ended,
+                                     end_on_miss=(feedback == "sample") if end_on_miss is None else end_on_miss)
         if not sync:
             return a_t, env_action, prev_angle
         return a_t, self.to_host(env_action), prev_angle

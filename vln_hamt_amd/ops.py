@@ -1415,6 +1415,8 @@ def policy_step(logit, cand_len, ended, mask, mode="sample", target=None, bt_mas
 NAV_TEACHER_MODES = {"path_step": 0, "path_index": 1, "shortest": 2}      # HAMT_NAV_*
 NAV_EVAL_COLS = ("nav_error", "oracle_error", "trajectory_steps", "trajectory_lengths", "success", "spl", "oracle_success", "DTW", "nDTW",
                  "SDTW", "CLS")
+NAV_GOALS_EVAL_COLS = ("trajectory_steps", "trajectory_lengths", "success", "oracle_success", "spl", "gp", "spl_ratio")
+NAV_BACK_EVAL_COLS = ("nav_error", "trajectory_steps", "trajectory_lengths", "success", "spl", "DTW", "nDTW", "SDTW", "CLS")
 
 
 def _nav_arg(name, t_, dt, shape, dev):
@@ -1471,6 +1473,83 @@ def nav_eval(graphs, scan, path, path_len, gt, gt_len):
     out = torch.empty(N, len(NAV_EVAL_COLS), dtype=torch.float64, device=dev)
     L.check(L.load().hamt_nav_eval(N, P, G, _p(graphs.dist), _p(graphs.scan_offset), _p(graphs.scan_n), _p(scan), _p(path), _p(path_len), _p(gt),
                                    _p(gt_len), _p(out), _stream()), "hamt_nav_eval")
+    return out
+
+
+def nav_advance_goals(ep, cand_node, env_action, mask, reward):
+    """`nav_advance` for episodes whose goal is a set of nodes (agent.GoalSetEpisodes: CVDN's end_panos, REVERIE's viewpoints the
+    object is visible from): the move, `last_dist` = the fp32 minimum distance over the set (0 for an empty set) and the reward of
+    cvdn/agent.py:174-203 = reverie/agent.py:337-366 -- a stop is right only AT a goal, a move earns +1 / -1 / 0 -- into `reward`."""
+    _chk(cand_node, "nav_advance_goals")
+    dev, (B, V), g = cand_node.device, cand_node.shape, ep.graphs
+    _nav_arg("nav_advance_goals: cand_node", cand_node, torch.int32, (ep.B, V), dev)
+    _nav_arg("nav_advance_goals: env_action", env_action, torch.int32, (B,), dev)
+    _nav_arg("nav_advance_goals: mask", mask, torch.float32, (B,), dev)
+    _nav_arg("nav_advance_goals: reward", reward, torch.float32, (B,), dev)
+    L.check(L.load().hamt_nav_advance_goals(B, V, ep.E_max, ep.path_cap, _p(g.dist), _p(g.scan_offset), _p(g.scan_n), _p(ep.scan), _p(cand_node),
+                                            _p(env_action), _p(mask), _p(ep.cur), _p(ep.goals), _p(ep.goal_len), _p(ep.path), _p(ep.path_len),
+                                            _p(ep.last_dist), _p(reward), _stream()), "hamt_nav_advance_goals")
+    return reward
+
+
+def nav_advance_back(ep, cand_node, env_action, mask, reward, ended, end_on_miss=True):
+    """`nav_advance` for return trips (agent.ReturnEpisodes, r2r/agent_r2rback.py:192-198 and :227-276), after the policy step has set
+    `ended` |= stop: the reward is judged against the mid-stop until the first STOP and against the path's end after it; the first
+    STOP records `ep.midstop_at`, sets `ep.first_ended` and takes `ended` back to 0 -- or, with `end_on_miss` (RL training), leaves the
+    episode ended when the mid-stop was missed by 3 m or more.  `ended` uint8 [B] is the recorder's, updated IN PLACE."""
+    _chk(cand_node, "nav_advance_back")
+    dev, (B, V), g = cand_node.device, cand_node.shape, ep.graphs
+    _nav_arg("nav_advance_back: cand_node", cand_node, torch.int32, (ep.B, V), dev)
+    _nav_arg("nav_advance_back: env_action", env_action, torch.int32, (B,), dev)
+    _nav_arg("nav_advance_back: mask", mask, torch.float32, (B,), dev)
+    _nav_arg("nav_advance_back: reward", reward, torch.float32, (B,), dev)
+    _nav_arg("nav_advance_back: ended", ended, torch.uint8, (B,), dev)
+    L.check(L.load().hamt_nav_advance_back(B, V, ep.G_max, ep.path_cap, int(bool(end_on_miss)), _p(g.dist), _p(g.scan_offset), _p(g.scan_n),
+                                           _p(ep.scan), _p(cand_node), _p(env_action), _p(mask), _p(ep.cur), _p(ep.goal), _p(ep.midstop), _p(ep.gt),
+                                           _p(ep.gt_len), _p(ep.path), _p(ep.path_len), _p(ep.dtw_row), _p(ep.last_dist), _p(ep.last_ndtw),
+                                           _p(ep.first_ended), _p(ep.midstop_at), _p(ended), _p(ep.anomalies), _p(reward), _stream()),
+            "hamt_nav_advance_back")
+    return reward
+
+
+def nav_eval_goals(graphs, scan, path, path_len, goals, goal_len, gt=None, gt_len=None):
+    """cvdn/env.py::_eval_item (no `gt`: gt_lengths is the start's distance to the nearest goal) or reverie/env.py::_eval_item's
+    navigation part (`gt` int32 [N, G_max]: gt_lengths is the ground-truth path's length) for N finished trajectories in one launch;
+    `goals` int32 [N, E_max <= 256] with `goal_len`.  Returns fp64 [N, 7] in the column order NAV_GOALS_EVAL_COLS."""
+    _chk(path, "nav_eval_goals")
+    dev, (N, P), E = path.device, path.shape, goals.shape[1]
+    _nav_arg("nav_eval_goals: scan", scan, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_goals: path", path, torch.int32, (N, P), dev)
+    _nav_arg("nav_eval_goals: path_len", path_len, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_goals: goals", goals, torch.int32, (N, E), dev)
+    _nav_arg("nav_eval_goals: goal_len", goal_len, torch.int32, (N,), dev)
+    G = 0
+    if gt is not None:
+        G = gt.shape[1]
+        _nav_arg("nav_eval_goals: gt", gt, torch.int32, (N, G), dev)
+        _nav_arg("nav_eval_goals: gt_len", gt_len, torch.int32, (N,), dev)
+    out = torch.empty(N, len(NAV_GOALS_EVAL_COLS), dtype=torch.float64, device=dev)
+    L.check(L.load().hamt_nav_eval_goals(N, P, E, G, _p(graphs.dist), _p(graphs.scan_offset), _p(graphs.scan_n), _p(scan), _p(path), _p(path_len),
+                                         _p(goals), _p(goal_len), _p(gt), _p(gt_len if gt is not None else None), _p(out), _stream()),
+            "hamt_nav_eval_goals")
+    return out
+
+
+def nav_eval_back(graphs, scan, path, path_len, gt, gt_len, midstop, gt_midstop):
+    """env.py::R2RBackBatch._eval_item for N finished return trips in one launch: `nav_eval`'s inputs plus `midstop` int32 [N] (where the
+    agent made its first STOP, -1 = never) and `gt_midstop` int32 [N].  Returns fp64 [N, 9] in the column order NAV_BACK_EVAL_COLS."""
+    _chk(path, "nav_eval_back")
+    dev, (N, P), G = path.device, path.shape, gt.shape[1]
+    _nav_arg("nav_eval_back: scan", scan, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_back: path", path, torch.int32, (N, P), dev)
+    _nav_arg("nav_eval_back: path_len", path_len, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_back: gt", gt, torch.int32, (N, G), dev)
+    _nav_arg("nav_eval_back: gt_len", gt_len, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_back: midstop", midstop, torch.int32, (N,), dev)
+    _nav_arg("nav_eval_back: gt_midstop", gt_midstop, torch.int32, (N,), dev)
+    out = torch.empty(N, len(NAV_BACK_EVAL_COLS), dtype=torch.float64, device=dev)
+    L.check(L.load().hamt_nav_eval_back(N, P, G, _p(graphs.dist), _p(graphs.scan_offset), _p(graphs.scan_n), _p(scan), _p(path), _p(path_len),
+                                        _p(gt), _p(gt_len), _p(midstop), _p(gt_midstop), _p(out), _stream()), "hamt_nav_eval_back")
     return out
 
 
