@@ -648,7 +648,12 @@ int hamt_adamw_table(size_t n, float* p, float* g, float* m, float* v, void* p16
                      const float* hyp, int nparams, const float* gnorm_sq, float max_norm, float beta1,
                      float beta2, float eps, int zero_grad, void* stream);
 /* the same over the arena elements [first, first + n) only (p, g, m, v, p16 point at element `first`; `ends` / `hyp` still
- * describe the whole arena): a rank of a sharded optimizer updates just the segments it owns (parallel.ShardedGradSync) */
+ * describe the whole arena): a rank of a sharded optimizer updates just the segments it owns (parallel.ShardedGradSync), the
+ * overlapped update one chunk per launch (optim.AdamW.launch_step_overlapped).  `first` and `n` are multiples of 4 (one 16-byte
+ * access never straddles two parameters: offsets are multiples of 8) and need be nothing more: a range may start and end INSIDE
+ * parameters, at any multiple of 4.  Nothing outside [first, first + n) is read or written, and an element's result does not
+ * depend on the range it is updated in: disjoint ranges that cover the arena give, in any order, bit for bit what one
+ * hamt_adamw_table launch gives (tests/test_gpu_adamw.py::test_adamw_table_range_union_is_the_whole). */
 int hamt_adamw_table_range(size_t first, size_t n, float* p, float* g, float* m, float* v, void* p16,
                            const int* ends, const float* hyp, int nparams, const float* gnorm_sq,
                            float max_norm, float beta1, float beta2, float eps, int zero_grad, void* stream);
