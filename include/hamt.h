@@ -535,6 +535,44 @@ int hamt_policy_step_bwd(int B, int V, int mode, int64_t ignoreid, const float* 
                          const uint8_t* bt_mask, const int64_t* action, const float* lse, const float* g_ml,
                          const float* g_logp, const float* g_ent, int gs_ml, int gs_logp, int gs_ent, float* dlogit, int ld_dlogit,
                          void* stream);
+/* REVERIE's rollout step (finetune_src/reverie/agent.py:253-307), one launch, one wave per row.  What differs from hamt_policy_step:
+ *   the row    V + 1 <= 256 columns: act_logit [B, V] (V = ob_img_max_len; fp32, row stride ld_act, -inf at everything that is not a
+ *              navigable candidate) and column V, STOP, made from obj_logit [B, O] (0 < O <= 256, row stride ld_obj, -inf at padding):
+ *              HAMT_STOP_LOGIT_INDEX (float) of the row's arg-max, as the reference writes it (:253-254 keeps torch.max's indices) -- no
+ *              gradient reaches obj_logit through the action row; HAMT_STOP_LOGIT_VALUE the maximum itself, whose gradient goes to the
+ *              arg-max element.  Ties: the lowest index.
+ *   ml         cross-entropy of the back-track-MASKED row (:269 precedes :274) against target[b]; a target that is not ignoreid and is
+ *              >= cand_len[b] - 1 (cand_len = navigable candidates + 1) means STOP and is read as V, so the reference's V and
+ *              hamt_nav_observe's cand_len - 1 both drive it.  bt_mask [B, V] uint8: column V is never masked.
+ *   ref        cross-entropy of obj_logit[b, :O] against ref_target[b] (:275; ignoreid = 0); ref_target NULL and obj_id int32 [B, O] +
+ *              goal_obj int32 [B] given: the first k < obj_len[b] with obj_id[b, k] == goal_obj[b] where the target is STOP and the
+ *              episode had not ended, else ignored (_teacher_action, :150-160).  Both NULL: ref = 0.
+ *   action     as hamt_policy_step over the V + 1 columns; teacher: the target with STOP read as V.
+ *   env_action -1 iff a_t >= V, a_t == ignoreid or ended_in (:306); no cand_len - 1 rule.  prev_angle from ob_ang [B, V, A].
+ *   pred_obj   int32 [B], written ONLY where (a_t >= V or last_step) and !ended_in (:299-304): -1 if obj_len[b] == 0 (obj_len is the
+ *              true count; the reference pads an empty list to one slot for the model, the prediction stays None), else the lowest
+ *              arg-max of obj_logit[b, :obj_len[b]].  pred_obj_id the same through obj_id (needs obj_id).  Either may be NULL.
+ *   lse [B, 3] log-sum-exp of the masked action row and of the object row, and column V's value; saved int32 [B, 3]: the object
+ *              arg-max and the effective ref / action targets.  With the inputs they are all the backward reads.
+ * mask, ended, hist_len, logp, ent, forced_action, uniform, rng, call_id: as hamt_policy_step_fwd.  A row without a finite column
+ * (VALUE with an object row of -inf) gives env_action -1, logp 0, ent 0 and zero gradients.
+ * bwd: dact [B, V] and dobj [B, O] of sum_b g_ml ml + g_ref ref + g_logp logp + g_ent ent (each g NULL = 0, read at b * gs_*, 0 or 1);
+ * column V's gradient is added to dobj[b, arg-max] (VALUE) or dropped (INDEX); masked and -inf positions get exactly 0. */
+#define HAMT_STOP_LOGIT_INDEX 0
+#define HAMT_STOP_LOGIT_VALUE 1
+int hamt_policy_ref_step_fwd(int B, int V, int O, int A, int mode, int stop_logit, int last_step, int64_t ignoreid,
+                             const float* act_logit, int ld_act, const float* obj_logit, int ld_obj, const int32_t* obj_len,
+                             const int32_t* cand_len, const int64_t* target, const int64_t* ref_target, const int32_t* obj_id,
+                             const int32_t* goal_obj, const uint8_t* bt_mask, uint8_t* ended, const float* ob_ang,
+                             const int64_t* forced_action, const float* uniform, const uint64_t* rng, uint32_t call_id,
+                             float* ml, float* ref, int64_t* action, float* logp, float* ent, float* mask, int32_t* env_action,
+                             float* prev_angle, int32_t* hist_len, int32_t* pred_obj, int32_t* pred_obj_id, float* lse,
+                             int32_t* saved, void* stream);
+int hamt_policy_ref_step_bwd(int B, int V, int O, int mode, int stop_logit, const float* act_logit, int ld_act,
+                             const float* obj_logit, int ld_obj, const uint8_t* bt_mask, const int64_t* action, const float* lse,
+                             const int32_t* saved, const float* g_ml, const float* g_ref, const float* g_logp, const float* g_ent,
+                             int gs_ml, int gs_ref, int gs_logp, int gs_ent, float* dact, int ld_dact, float* dobj, int ld_dobj,
+                             void* stream);
 /* The navigation-graph side of a rollout step and the evaluation metrics (csrc/nav.hip).  The graphs of all scans lie in one arena:
  * scan s has scan_n[s] nodes and owns the elements [scan_off[s], scan_off[s] + n * n) of `dist` (fp64, all-pairs shortest distances,
  * dist[x * n + y]) and `nxt` (int32, the next hop from x toward y; nxt[x, x] = x).  Node ids are local to their scan.  Episode b:

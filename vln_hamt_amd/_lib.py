@@ -159,6 +159,8 @@ SIGNATURES = {
     "hamt_a2c_bwd": [i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp],
     "hamt_policy_step_fwd": [i32, i32, i32, i32, C.c_int64, vp, i32] + [vp] * 8 + [u32] + [vp] * 10,
     "hamt_policy_step_bwd": [i32, i32, i32, C.c_int64, vp, i32] + [vp] * 7 + [i32, i32, i32, vp, i32, vp],
+    "hamt_policy_ref_step_fwd": [i32] * 7 + [C.c_int64, vp, i32, vp, i32] + [vp] * 12 + [u32] + [vp] * 14,
+    "hamt_policy_ref_step_bwd": [i32] * 5 + [vp, i32, vp, i32] + [vp] * 8 + [i32] * 4 + [vp, i32, vp, i32, vp],
     "hamt_nav_observe": [i32, i32, i32, i32, C.c_int64, i32, i32] + [vp] * 17,
     "hamt_nav_advance": [i32, i32, i32, i32] + [vp] * 19,
     "hamt_nav_eval": [i32, i32, i32] + [vp] * 10,

@@ -1412,6 +1412,99 @@ def policy_step(logit, cand_len, ended, mask, mode="sample", target=None, bt_mas
                               ignoreid, next_call_id() if call_id is None else call_id, out)
 
 
+STOP_LOGITS = {"index": 0, "value": 1}                       # HAMT_STOP_LOGIT_*
+
+
+def _grad_arg(g):
+    """a [B] gradient with element stride 1 or 0 (the expanded gradient of a plain sum) goes in as it is: no copy kernel"""
+    if g is None:
+        return None, 0
+    if g.dtype != torch.float32 or g.stride(0) not in (0, 1):
+        g = g.to(torch.float32).contiguous()
+    return g, g.stride(0)
+
+
+class PolicyRefStepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, act_logit, obj_logit, obj_len, cand_len, ended, mask, target, ref_target, obj_id, goal_obj, bt_mask, ob_ang, hist_len,
+                forced_action, uniform, mode, stop_logit, last_step, ignoreid, call_id, pred_obj, pred_obj_id, out):
+        _chk(act_logit, "policy_ref_step")
+        if act_logit.dim() != 2 or obj_logit.dim() != 2 or obj_logit.shape[0] != act_logit.shape[0] or obj_logit.device != act_logit.device:
+            raise L.HamtError(f"policy_ref_step: act_logit [B, V] and obj_logit [B, O] on one device, got {tuple(act_logit.shape)} on "
+                              f"{act_logit.device} and {tuple(obj_logit.shape)} on {obj_logit.device}")
+        x, xo = act_logit.detach(), obj_logit.detach()
+        if x.dtype != torch.float32 or x.stride(1) != 1:
+            x = x.to(torch.float32).contiguous()
+        if xo.dtype != torch.float32 or xo.stride(1) != 1:
+            xo = xo.to(torch.float32).contiguous()
+        (B, V), O = x.shape, xo.shape[1]
+        dev = x.device
+        A = 0 if ob_ang is None else ob_ang.shape[-1]
+        i32_, i64_, u8_, f32_ = torch.int32, torch.int64, torch.uint8, torch.float32
+        for name, t_, dt, shape in (("obj_len", obj_len, i32_, (B,)), ("cand_len", cand_len, i32_, (B,)), ("ended", ended, u8_, (B,)),
+                                    ("mask", mask, f32_, (B,)), ("target", target, i64_, (B,)), ("ref_target", ref_target, i64_, (B,)),
+                                    ("obj_id", obj_id, i32_, (B, O)), ("goal_obj", goal_obj, i32_, (B,)), ("bt_mask", bt_mask, u8_, (B, V)),
+                                    ("ob_ang", ob_ang, f32_, (B, V, A)), ("hist_len", hist_len, i32_, (B,)),
+                                    ("forced_action", forced_action, i64_, (B,)), ("uniform", uniform, f32_, (B,)),
+                                    ("pred_obj", pred_obj, i32_, (B,)), ("pred_obj_id", pred_obj_id, i32_, (B,))):
+            if t_ is not None and (t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous() or t_.device != dev):
+                raise L.HamtError(f"policy_ref_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+        if (obj_id is None) != (goal_obj is None) and ref_target is None:
+            raise L.HamtError("policy_ref_step: the object target comes from ref_target, or from obj_id AND goal_obj")
+        ml, ref, logp, ent = out if out is not None else (torch.empty(B, dtype=f32_, device=dev) for _ in range(4))
+        action = torch.empty(B, dtype=i64_, device=dev)
+        env_action = torch.empty(B, dtype=i32_, device=dev)
+        prev_angle = torch.empty(B, A, dtype=f32_, device=dev)
+        lse = torch.empty(B, 3, dtype=f32_, device=dev)
+        saved = torch.empty(B, 3, dtype=i32_, device=dev)
+        L.check(L.load().hamt_policy_ref_step_fwd(
+            B, V, O, A, mode, stop_logit, int(bool(last_step)), int(ignoreid), _p(x), x.stride(0), _p(xo), xo.stride(0), _p(obj_len), _p(cand_len),
+            _p(target), _p(ref_target), _p(obj_id), _p(goal_obj), _p(bt_mask), _p(ended), _p(ob_ang), _p(forced_action), _p(uniform),
+            _p(rng_state(dev)), int(call_id), _p(ml), _p(ref), _p(action), _p(logp), _p(ent), _p(mask), _p(env_action),
+            _p(prev_angle) if A else None, _p(hist_len), _p(pred_obj), _p(pred_obj_id) if obj_id is not None else None, _p(lse), _p(saved),
+            _stream()), "hamt_policy_ref_step_fwd")
+        ctx.save_for_backward(x, xo, bt_mask, action, lse, saved)
+        ctx.meta = (mode, stop_logit)
+        ctx.mark_non_differentiable(action, env_action, prev_angle)
+        ctx.set_materialize_grads(False)
+        if mode != POLICY_MODES["sample"]:
+            ent = None
+        return ml, ref, logp, ent, action, env_action, prev_angle
+
+    @staticmethod
+    def backward(ctx, g_ml, g_ref, g_logp, g_ent, *_):
+        x, xo, bt_mask, action, lse, saved = ctx.saved_tensors
+        mode, stop_logit = ctx.meta
+        (B, V), O = x.shape, xo.shape[1]
+        (g_ml, s_ml), (g_ref, s_ref), (g_logp, s_logp), (g_ent, s_ent) = _grad_arg(g_ml), _grad_arg(g_ref), _grad_arg(g_logp), _grad_arg(g_ent)
+        dx = torch.empty(B, V, dtype=torch.float32, device=x.device)
+        dxo = torch.empty(B, O, dtype=torch.float32, device=x.device)
+        L.check(L.load().hamt_policy_ref_step_bwd(B, V, O, mode, stop_logit, _p(x), x.stride(0), _p(xo), xo.stride(0), _p(bt_mask), _p(action),
+                                                  _p(lse), _p(saved), _p(g_ml), _p(g_ref), _p(g_logp), _p(g_ent), s_ml, s_ref, s_logp, s_ent,
+                                                  _p(dx), V, _p(dxo), O, _stream()), "hamt_policy_ref_step_bwd")
+        return (dx, dxo) + (None,) * 21
+
+
+def policy_ref_step(act_logit, obj_logit, obj_len, cand_len, ended, mask, mode="sample", stop_logit="index", target=None, ref_target=None,
+                    obj_id=None, goal_obj=None, bt_mask=None, ob_ang=None, hist_len=None, forced_action=None, uniform=None, last_step=False,
+                    ignoreid=-100, call_id=None, pred_obj=None, pred_obj_id=None, out=None):
+    """`policy_step` for REVERIE's agent (finetune_src/reverie/agent.py:253-307), one launch and one more for its backward.
+    `act_logit` [B, V] (V = ob_img_max_len, V + 1 <= 256) and `obj_logit` [B, O <= 256] are the differentiable inputs; the action row is
+    act_logit plus ONE column V that stands for STOP: with stop_logit='index' the best object's INDEX as a float, exactly what the
+    reference writes (:253-254; no gradient reaches obj_logit through the action row), with 'value' the best object's logit (its
+    gradient goes to the arg-max element; ties: the lowest index).  The imitation cross-entropy is taken on the back-track-MASKED row
+    (:269, :274); a `target` >= cand_len - 1 means STOP (the reference's V and nav_observe's cand_len - 1 alike).  The object
+    cross-entropy `ref` (:275) reads `ref_target` [B] int64, or derives it from `obj_id` int32 [B, O] and `goal_obj` int32 [B]: the
+    goal's first slot where the teacher says STOP, else ignored.  `obj_len` int32 [B] is the TRUE object count (0 allowed).
+    env_action is -1 iff a_t >= V, a_t == ignoreid or the episode had ended.  `pred_obj` / `pred_obj_id` int32 [B] are updated IN PLACE
+    like `ended`, `mask`, `hist_len`: where (a_t >= V or `last_step`) and the episode had not ended, the arg-max of
+    obj_logit[b, :obj_len[b]] and its id, -1 for a viewpoint without objects (:299-304).  `out` = (ml, ref, logp, ent).
+    Returns (ml, ref, logp, ent, action, env_action, prev_angle)."""
+    return PolicyRefStepFn.apply(act_logit, obj_logit, obj_len, cand_len, ended, mask, target, ref_target, obj_id, goal_obj, bt_mask, ob_ang,
+                                 hist_len, forced_action, uniform, POLICY_MODES[mode], STOP_LOGITS[stop_logit], last_step, ignoreid,
+                                 next_call_id() if call_id is None else call_id, pred_obj, pred_obj_id, out)
+
+
 NAV_TEACHER_MODES = {"path_step": 0, "path_index": 1, "shortest": 2}      # HAMT_NAV_*
 NAV_EVAL_COLS = ("nav_error", "oracle_error", "trajectory_steps", "trajectory_lengths", "success", "spl", "oracle_success", "DTW", "nDTW",
                  "SDTW", "CLS")
