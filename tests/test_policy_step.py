@@ -129,10 +129,10 @@ def test_policy_kernels_use_no_scratch(tmp_path):
         notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True).stdout
         for blk in notes.split("- .agpr_count:")[1:]:
             name = re.search(r"\.name:\s+(\S+)", blk)
-            if not name or "policy_step_" not in name.group(1):
+            if not name or not re.search(r"policy_(step|ref)_(fwd|bwd)_kernel", name.group(1)):
                 continue
             num = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", blk).group(1))
             seen.append(name.group(1))
             assert num("vgpr_spill_count") == 0 and num("sgpr_spill_count") == 0 and num("private_segment_fixed_size") == 0, (name.group(1), blk)
             assert num("group_segment_fixed_size") == 0, name.group(1)                         # wave reductions only: no LDS
-    assert len(seen) == 2 and any("fwd" in s for s in seen) and any("bwd" in s for s in seen), seen
+    assert len(seen) == 4 and all(sum(k in s for s in seen) == 1 for k in ("policy_step_fwd", "policy_step_bwd", "policy_ref_fwd", "policy_ref_bwd")), seen

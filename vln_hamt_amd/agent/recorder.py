@@ -121,38 +121,56 @@ class RolloutRecorder:
         `ops.nav_advance_goals`; a ReturnEpisodes (R2R-Back) takes `ops.nav_advance_back`, which also reads and writes `ended` (the first
         STOP does not end a return trip) -- `end_on_miss` (a missed mid-stop ends the episode, agent_r2rback.py:252, which sits under
         `if train_rl:`) defaults to feedback == 'sample'."""
+        cand_lens, target, bt_mask = self._begin_step(t, cand_lens, target, bt_mask, nav, cand_nodes, teacher_mode)
+        ml, logp, ent, a_t, env_action, prev_angle = ops.policy_step(
+            logit, cand_lens, self.ended, self._row(self.mask, t), mode=feedback, target=target, bt_mask=bt_mask, ob_ang=ob_ang_feats,
+            hist_len=self.hist_len, forced_action=forced_action, uniform=uniform, ignoreid=self.ignoreid,
+            call_id=(self.call_id + t) & 0xFFFFFFFF, out=tuple(self._row(b_, t) for b_ in (self.ml, self.logp, self.ent)))
+        return self._end_step(t, feedback, {"ml": ml, "logp": logp, "ent": ent}, a_t, env_action, prev_angle, nav, cand_nodes, sync, end_on_miss)
+
+    def _row(self, buf, t):
+        """row t of one of the [T_max, B] arrays, as a [B] tensor of its own (see _alias)"""
+        return _alias(buf, t * self.B, (self.B,))
+
+    def _upload_i32(self, v):
+        """an int32 device tensor as it is; a host list uploaded"""
+        return v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.int32)).to(self.device, non_blocking=True)
+
+    def _begin_step(self, t, cand_lens, target, bt_mask, nav, cand_nodes, teacher_mode):
+        """What precedes the policy launch of step t: the order check, dropping the rows of a step recorded again, the upload of a host
+        `cand_lens`, and with `nav` the teacher's slot and the back-track mask of `ops.nav_observe` for whichever of `target` / `bt_mask`
+        is None (False = none).  Returns (cand_lens, target, bt_mask) as the launch takes them."""
+        me = type(self).__name__
         if t > self.steps or t >= self.T_max:
-            raise ops.L.HamtError(f"RolloutRecorder.step: step {t} after {self.steps} recorded steps (T_max {self.T_max})")
+            raise ops.L.HamtError(f"{me}.step: step {t} after {self.steps} recorded steps (T_max {self.T_max})")
         for rows in self._rows.values():         # (a step recorded again -- the warm-up and the capture of a graphed step -- replaces its row)
             del rows[t:]
-        if not torch.is_tensor(cand_lens):
-            cand_lens = torch.as_tensor(np.asarray(cand_lens, dtype=np.int32)).to(self.device, non_blocking=True)
-        B = self.B
+        cand_lens = self._upload_i32(cand_lens)
         if nav is not None:
             if cand_nodes is None:
-                raise ops.L.HamtError("RolloutRecorder.step: nav= needs cand_nodes (int32 [B, V], the node of every navigable candidate)")
+                raise ops.L.HamtError(f"{me}.step: nav= needs cand_nodes (int32 [B, V], the node of every navigable candidate)")
             tgt, btm = ops.nav_observe(nav, t, cand_nodes, cand_lens, self.ended, mode=teacher_mode, ignoreid=self.ignoreid,
                                        target=target is None, bt_mask=bt_mask is None)
             target, bt_mask = (tgt if target is None else target), (btm if bt_mask is None else bt_mask)
         target, bt_mask = (None if target is False else target), (None if bt_mask is False else bt_mask)
         self.target, self.bt_mask = target, bt_mask          # (what this step used: device tensors, for the caller's logs)
-        out = tuple(_alias(b_, t * B, (B,)) for b_ in (self.ml, self.logp, self.ent))
-        ml, logp, ent, a_t, env_action, prev_angle = ops.policy_step(
-            logit, cand_lens, self.ended, _alias(self.mask, t * B, (B,)), mode=feedback, target=target, bt_mask=bt_mask, ob_ang=ob_ang_feats,
-            hist_len=self.hist_len, forced_action=forced_action, uniform=uniform, ignoreid=self.ignoreid,
-            call_id=(self.call_id + t) & 0xFFFFFFFF, out=out)
-        self._rows["ml"].append(ml)
-        self._rows["logp"].append(logp)
-        self._rows["ent"].append(ent)
+        return cand_lens, target, bt_mask
+
+    def _end_step(self, t, feedback, rows, a_t, env_action, prev_angle, nav, cand_nodes, sync, end_on_miss):
+        """What follows the policy launch of step t: record its `rows` ({name: [B] autograd tensor}), with `nav` move the episodes and
+        write the reward (the launch the episodes' kind asks for), and hand the environment action to the host unless sync=False."""
+        for name, r in rows.items():
+            self._rows[name].append(r)
         self.feedback = feedback
         if nav is not None:
             kind = getattr(nav, "KIND", "r2r")
+            mask, reward = self._row(self.mask, t), self._row(self.reward, t)
             if kind == "r2r":
-                ops.nav_advance(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
+                ops.nav_advance(nav, cand_nodes, env_action, mask, reward)
             elif kind == "goals":
-                ops.nav_advance_goals(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)))
+                ops.nav_advance_goals(nav, cand_nodes, env_action, mask, reward)
             else:
-                ops.nav_advance_back(nav, cand_nodes, env_action, _alias(self.mask, t * B, (B,)), _alias(self.reward, t * B, (B,)), self.ended,
+                ops.nav_advance_back(nav, cand_nodes, env_action, mask, reward, self.ended,
                                      end_on_miss=(feedback == "sample") if end_on_miss is None else end_on_miss)
         if not sync:
             return a_t, env_action, prev_angle

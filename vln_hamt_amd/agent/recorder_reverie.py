@@ -8,7 +8,6 @@ and the step's one transfer to the host is still the int32 environment action; t
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
 from .. import ops
@@ -51,40 +50,18 @@ class ReverieRolloutRecorder(RolloutRecorder):
         `obj_ids` int32 [B, O] and `goal_obj` int32 [B]; `obj_ids` also fills `pred_obj_id`.  `nav` (a GoalSetEpisodes) with
         `cand_nodes`: `ops.nav_observe` -> `ops.policy_ref_step` -> `ops.nav_advance_goals`, as the base class does.  The step is the
         rollout's last one, which predicts an object for every episode still running, when t == T_max - 1."""
-        if t > self.steps or t >= self.T_max:
-            raise ops.L.HamtError(f"ReverieRolloutRecorder.step: step {t} after {self.steps} recorded steps (T_max {self.T_max})")
-        for rows in self._rows.values():
-            del rows[t:]
-        if not torch.is_tensor(cand_lens):
-            cand_lens = torch.as_tensor(np.asarray(cand_lens, dtype=np.int32)).to(self.device, non_blocking=True)
-        if not torch.is_tensor(obj_lens):
-            obj_lens = torch.as_tensor(np.asarray(obj_lens, dtype=np.int32)).to(self.device, non_blocking=True)
-        B = self.B
-        if nav is not None:
-            if cand_nodes is None:
-                raise ops.L.HamtError("ReverieRolloutRecorder.step: nav= needs cand_nodes (int32 [B, V], the node of every navigable candidate)")
-            if getattr(nav, "KIND", "r2r") != "goals":
-                raise ops.L.HamtError("ReverieRolloutRecorder.step: nav= must be a GoalSetEpisodes")
-            tgt, btm = ops.nav_observe(nav, t, cand_nodes, cand_lens, self.ended, mode=teacher_mode, ignoreid=self.ignoreid,
-                                       target=target is None, bt_mask=bt_mask is None)
-            target, bt_mask = (tgt if target is None else target), (btm if bt_mask is None else bt_mask)
-        target, bt_mask = (None if target is False else target), (None if bt_mask is False else bt_mask)
-        self.target, self.bt_mask = target, bt_mask
-        row = lambda buf: _alias(buf, t * B, (B,))
+        if nav is not None and getattr(nav, "KIND", "r2r") != "goals":
+            raise ops.L.HamtError("ReverieRolloutRecorder.step: nav= must be a GoalSetEpisodes")
+        cand_lens, target, bt_mask = self._begin_step(t, cand_lens, target, bt_mask, nav, cand_nodes, teacher_mode)
         ml, ref, logp, ent, a_t, env_action, prev_angle = ops.policy_ref_step(
-            act_logit, obj_logit, obj_lens, cand_lens, self.ended, row(self.mask), mode=feedback, stop_logit=stop_logit, target=target,
-            ref_target=ref_target, obj_id=obj_ids, goal_obj=goal_obj, bt_mask=bt_mask, ob_ang=ob_ang_feats, hist_len=self.hist_len,
-            forced_action=forced_action, uniform=uniform, last_step=(t == self.T_max - 1), ignoreid=self.ignoreid,
-            call_id=(self.call_id + t) & 0xFFFFFFFF, pred_obj=self.pred_obj, pred_obj_id=self.pred_obj_id if obj_ids is not None else None,
-            out=tuple(row(b_) for b_ in (self.ml, self.ref, self.logp, self.ent)))
-        for name, r in (("ml", ml), ("ref", ref), ("logp", logp), ("ent", ent)):
-            self._rows[name].append(r)
-        self.feedback = feedback
-        if nav is not None:
-            ops.nav_advance_goals(nav, cand_nodes, env_action, row(self.mask), row(self.reward))
-        if not sync:
-            return a_t, env_action, prev_angle
-        return a_t, self.to_host(env_action), prev_angle
+            act_logit, obj_logit, self._upload_i32(obj_lens), cand_lens, self.ended, self._row(self.mask, t), mode=feedback,
+            stop_logit=stop_logit, target=target, ref_target=ref_target, obj_id=obj_ids, goal_obj=goal_obj, bt_mask=bt_mask,
+            ob_ang=ob_ang_feats, hist_len=self.hist_len, forced_action=forced_action, uniform=uniform, last_step=(t == self.T_max - 1),
+            ignoreid=self.ignoreid, call_id=(self.call_id + t) & 0xFFFFFFFF, pred_obj=self.pred_obj,
+            pred_obj_id=self.pred_obj_id if obj_ids is not None else None,
+            out=tuple(self._row(b_, t) for b_ in (self.ml, self.ref, self.logp, self.ent)))
+        return self._end_step(t, feedback, {"ml": ml, "ref": ref, "logp": logp, "ent": ent}, a_t, env_action, prev_angle, nav, cand_nodes,
+                              sync, None)
 
     def predicted_objects(self):
         """(slot, id) int32 numpy [B] of every episode's predicted object, -1 = none (`predObjId` None, agent.py:193, :301): ONE

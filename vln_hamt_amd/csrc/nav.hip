@@ -24,11 +24,6 @@ constexpr int kGoalChunks = HAMT_NAV_MAX_GOALS / 64;   // goal nodes per lane
 constexpr double kInf = __builtin_huge_val();
 constexpr double kMargin = 3.0;                    // ERROR_MARGIN of env.py, `threshold` of cal_dtw / cal_cls
 
-__device__ __forceinline__ int wave_min_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ double wave_min_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
@@ -222,7 +217,7 @@ __global__ __launch_bounds__(64 * kWaves) void nav_observe_kernel(
       int first = 0x7fffffff;                               // path.index(here)
       for (int j = lane; j < G; j += 64)
         if (g[j] == here) first = min(first, j);
-      first = wave_min_int(first);
+      first = wave_min_i(first);
       if (first != 0x7fffffff) tv = first == G - 1 ? here : g[first + 1];
     } else {
       const int to = goal[b];
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(64 * kWaves) void nav_observe_kernel(
     if (tv >= 0)
       for (int c = lane; c < nav; c += 64)
         if (cn[c] == tv) slot = min(slot, c);
-    slot = wave_min_int(slot);
+    slot = wave_min_i(slot);
     if (lane == 0) {
       long long a = ignoreid;
       if (!ended[b]) {

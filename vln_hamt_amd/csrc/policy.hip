@@ -1,28 +1,24 @@
-// The decision and loss side of ONE rollout step of the finetune agents (finetune_src/r2r/agent_cmt.py:336-401, repeated verbatim by
-// the R2R-back, CVDN and REVERIE agents), for all B episodes in one launch:
-//   imitation cross-entropy on the raw logits (:339)  ->  back-track mask (:350)  ->  teacher / argmax / sample choice with its
-//   log-probability and entropy (:353-366)  ->  environment action (:372-375), the chosen candidate's angle feature (:382-385),
-//   `ended` (:447), the A2C mask (:418-420) and the history lengths (:399-401).
-// One wave per row, lanes strided over the V <= 256 columns (4 per lane, held in registers), wave reductions only: no LDS, no atomics,
+// The decision and loss side of ONE rollout step of the finetune agents, for all B episodes in one launch.  Three parts:
+//   1. the shared row core: what every agent's step does to a row of logits -- the draw, the inverse-CDF sampler, the arg-max, log pi(a_t),
+//      the entropy, the book-keeping stores, and the backward's log-probability and entropy terms.  Each exists once, here.
+//   2. the R2R-family step (finetune_src/r2r/agent_cmt.py:336-401, repeated verbatim by the R2R-back and CVDN agents):
+//      imitation cross-entropy on the raw logits (:339)  ->  back-track mask (:350)  ->  teacher / argmax / sample choice with its
+//      log-probability and entropy (:353-366)  ->  environment action (:372-375), the chosen candidate's angle feature (:382-385),
+//      `ended` (:447), the A2C mask (:418-420) and the history lengths (:399-401).
+//   3. REVERIE's step (finetune_src/reverie/agent.py:253-307): the same with one more action column, STOP, made from the object logits,
+//      the cross-entropy AFTER the mask, and a second cross-entropy that grounds the object.
+// One wave per row, lanes strided over the <= 256 columns (4 per lane, held in registers), wave reductions only: no LDS, no atomics,
 // no hand-off between rows.  Every per-row result is stored by lane 0 with ordinary (vector) stores.
 #include "common.h"
 #include <float.h>
 
 namespace {
 
-constexpr int kCols = 4;                 // columns per lane: V <= 64 * kCols
+constexpr int kCols = 4;                 // columns per lane: at most 64 * kCols columns in a row
 constexpr int kRowsPerBlock = 4;         // waves per 256-thread workgroup
+constexpr int kNone = 0x7fffffff;        // "no slot" under wave_min_i
 
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// ---------------------------------------------------------------------------------------------------------------- 1. the shared row core
 // exp(x - ref) with exp(-inf - anything) = 0 (never -inf - -inf = NaN)
 __device__ __forceinline__ float exp_rel(float x, float ref) { return x == -INFINITY ? 0.f : expf(x - ref); }
 
@@ -36,14 +32,74 @@ __device__ __forceinline__ void row_max_sum(const float (&x)[kCols], float& m, f
 }
 __device__ __forceinline__ float lse_of(float m, float s) { return m == -INFINITY ? -INFINITY : m + logf(s); }
 
-__device__ __forceinline__ void load_row(const float* __restrict__ xr, const uint8_t* __restrict__ mr, int V, int lane,
-                                         float (&x)[kCols], float (&xm)[kCols]) {
+// lowest index among the columns c < n whose value equals m, the wave's maximum over them (torch.max's tie rule on one device); n <= 0: -1.
+// A dead row (all -inf) has every column equal to the maximum: slot 0.  A row where nothing compares equal (all NaN): slot 0 too.
+__device__ __forceinline__ int row_argmax(const float (&x)[kCols], int n, int lane, float m) {
+  int first = kNone;
+#pragma unroll
+  for (int k = kCols - 1; k >= 0; --k)
+    if (lane + 64 * k < n && x[k] == m) first = lane + 64 * k;
+  first = wave_min_i(first);
+  return first == kNone ? (n > 0 ? 0 : -1) : first;
+}
+// ... for a caller that has no maximum over exactly those columns yet
+__device__ __forceinline__ int row_argmax(const float (&x)[kCols], int n, int lane) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < kCols; ++k)
+    if (lane + 64 * k < n) m = fmaxf(m, x[k]);
+  return row_argmax(x, n, lane, wave_max(m));
+}
+
+// the draw of 'sample': the injected value, or a counter hash of (seed, epoch, call_id, row) as a 24-bit uniform in [0, 1)
+__device__ __forceinline__ float step_uniform(const float* __restrict__ uniform, const uint64_t* __restrict__ rng, uint32_t call_id, int b) {
+  if (uniform) return uniform[b];
+  const RngKey key = rng_key(rng, call_id);
+  uint32_t h = hamt_mix32((uint32_t)b ^ key.k0);
+  h = hamt_mix32(h + key.k1);
+  return (float)(h >> 8) * (1.0f / 16777216.0f);
+}
+
+// inverse CDF over the first n columns of a row with maximum m and sum s: the first slot of non-zero probability whose inclusive
+// cumulative probability exceeds u (the fp32 wave scan is not guaranteed monotone to the last bit: a slot of probability 0 is never
+// taken, whatever its rounded sum says); none: the last such slot; a dead row: slot 0
+__device__ __forceinline__ int sample_slot(const float (&xm)[kCols], int n, float m, float s, bool dead, float u, int lane) {
+  const float inv_s = dead ? 0.f : 1.0f / s;
+  float base = 0.f;
+  int first = kNone, last = -1;
 #pragma unroll
   for (int k = 0; k < kCols; ++k) {
-    const int v = lane + 64 * k;
-    x[k] = v < V ? xr[v] : -INFINITY;
-    xm[k] = (mr && v < V && mr[v]) ? -INFINITY : x[k];
+    if (64 * k < n) {                                       // (wave-uniform)
+      const int v = lane + 64 * k;
+      const float e = exp_rel(xm[k], m);
+      float scan = e;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(scan, o, 64);
+        if (lane >= o) scan += up;
+      }
+      if (e > 0.f) {
+        last = v;
+        if (first == kNone && (base + scan) * inv_s > u) first = v;
+      }
+      base += __shfl(scan, 63, 64);
+    }
   }
+  first = wave_min_i(first);
+  last = wave_max_i(last);
+  const int a = first != kNone ? first : last;
+  return a < 0 ? 0 : a;
+}
+
+// a_t over the first n columns of the masked row (m, s: their maximum and sum of exp(x - m); the columns behind them hold -inf):
+// forced, the teacher's target, the arg-max or a sample (:353-366)
+__device__ __forceinline__ long long choose_action(int mode, const int64_t* __restrict__ forced, long long tgt, const float (&xm)[kCols], int n,
+                                                   float m, float s, bool dead, const float* __restrict__ uniform,
+                                                   const uint64_t* __restrict__ rng, uint32_t call_id, int b, int lane) {
+  if (forced) return (long long)forced[b];
+  if (mode == HAMT_POLICY_TEACHER) return tgt;
+  if (mode == HAMT_POLICY_ARGMAX) return row_argmax(xm, n, lane, m);
+  return sample_slot(xm, n, m, s, dead, step_uniform(uniform, rng, call_id, b), lane);
 }
 
 // log pi(a) of the masked row as the reference takes it: log_softmax(...).gather (argmax, :358-359) or Categorical(probs).log_prob
@@ -61,6 +117,83 @@ __device__ __forceinline__ float chosen_logp(int mode, float xa, float lse1, boo
   return lp;
 }
 
+// entropy of the masked row ('sample' only: Categorical(probs).entropy(), :364); a dead row: 0
+__device__ __forceinline__ float row_entropy(const float (&xm)[kCols], float lse, bool dead) {
+  float H = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    const float p = exp_rel(xm[k], lse);
+    if (p > 0.f) H -= p * (xm[k] - lse);                     // 0 log 0 = 0
+  }
+  H = wave_sum(H);
+  return dead ? 0.f : H;
+}
+
+// the step's tail: the chosen candidate's angle feature (all lanes) and the per-row results and in-place state (lane 0); env < 0 = no move
+__device__ __forceinline__ void store_step(int b, int lane, int V, int A, int mode, bool was_ended, int env, float ml_b, long long a, float lp,
+                                           float H, const float* __restrict__ ob_ang, float* __restrict__ prev_angle, float* __restrict__ ml,
+                                           int64_t* __restrict__ action, float* __restrict__ logp, float* __restrict__ ent,
+                                           float* __restrict__ mask, int32_t* __restrict__ env_action, uint8_t* ended, int32_t* hist_len) {
+  if (prev_angle) {
+    for (int j = lane; j < A; j += 64)
+      prev_angle[(size_t)b * A + j] = (env >= 0 && ob_ang) ? ob_ang[((size_t)b * V + env) * A + j] : 0.f;
+  }
+  if (lane == 0) {
+    ml[b] = ml_b;
+    action[b] = (int64_t)a;
+    logp[b] = lp;
+    if (mode == HAMT_POLICY_SAMPLE && ent) ent[b] = H;
+    mask[b] = was_ended ? 0.f : 1.f;
+    env_action[b] = env;
+    ended[b] = (was_ended || env < 0) ? 1 : 0;
+    if (hist_len && !was_ended) hist_len[b] += 1;
+  }
+}
+
+// The backward's policy terms of one row: d(g_logp * log pi(a) + g_ent * H) / d(masked logit).  `p[]` doubles as the softmax of the
+// masked row for the caller's cross-entropy term.
+struct PolicyGrad {
+  float gl, ge, H, lse1, p[kCols];
+  bool with_ent;
+  // column k holding masked logit x (not -inf: such positions take nothing), added to d; `chosen` = this column is a_t
+  __device__ __forceinline__ float add(float d, int k, float x, bool chosen) const {
+    if (gl != 0.f) d += gl * ((chosen ? 1.f : 0.f) - p[k]);
+    if (with_ent && p[k] > 0.f) d += ge * (-p[k] * ((x - lse1) + H));
+    return d;
+  }
+};
+__device__ __forceinline__ PolicyGrad policy_grad_row(int mode, const float (&xm)[kCols], float xa, bool a_ok, float lse1, int b,
+                                                      const float* __restrict__ g_logp, const float* __restrict__ g_ent, int gs_logp,
+                                                      int gs_ent) {
+  PolicyGrad g;
+  bool live;
+  chosen_logp(mode, xa, lse1, a_ok, live);
+  const bool dead = lse1 == -INFINITY;
+  g.lse1 = lse1;
+  g.gl = (g_logp && live && mode != HAMT_POLICY_TEACHER) ? g_logp[(size_t)b * gs_logp] : 0.f;
+  g.with_ent = g_ent && mode == HAMT_POLICY_SAMPLE && !dead;
+  g.ge = g.with_ent ? g_ent[(size_t)b * gs_ent] : 0.f;
+  g.H = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    g.p[k] = dead ? 0.f : exp_rel(xm[k], lse1);
+    if (g.p[k] > 0.f) g.H -= g.p[k] * (xm[k] - lse1);
+  }
+  if (g.with_ent) g.H = wave_sum(g.H);                      // (wave-uniform condition)
+  return g;
+}
+
+// ---------------------------------------------------------------------------------------------------- 2. the R2R-family step
+__device__ __forceinline__ void load_row(const float* __restrict__ xr, const uint8_t* __restrict__ mr, int V, int lane,
+                                         float (&x)[kCols], float (&xm)[kCols]) {
+#pragma unroll
+  for (int k = 0; k < kCols; ++k) {
+    const int v = lane + 64 * k;
+    x[k] = v < V ? xr[v] : -INFINITY;
+    xm[k] = (mr && v < V && mr[v]) ? -INFINITY : x[k];
+  }
+}
+
 __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_fwd_kernel(
     int B, int V, int A, int mode, long long ignoreid, const float* __restrict__ logit, int ld, const int64_t* __restrict__ target,
     const uint8_t* __restrict__ bt_mask, const int32_t* __restrict__ cand_len, uint8_t* ended, const float* __restrict__ ob_ang,
@@ -75,7 +208,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_fwd_kernel(
   float x[kCols], xm[kCols];
   load_row(xr, mr, V, lane, x, xm);
 
-  // ---- imitation cross-entropy on the UNMASKED row (:339 precedes :350)
+  // ---- imitation cross-entropy on the UNMASKED row (:339 precedes :350; REVERIE's follows the mask)
   float m0, s0;
   row_max_sum(x, m0, s0);
   const float lse0 = lse_of(m0, s0);
@@ -88,59 +221,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_fwd_kernel(
   if (mr) row_max_sum(xm, m1, s1);
   const float lse1 = lse_of(m1, s1);
   const bool dead = m1 == -INFINITY;                        // every slot masked: cannot occur on the path (the STOP slot is never visited)
-
-  long long a;
-  if (forced) {
-    a = (long long)forced[b];
-  } else if (mode == HAMT_POLICY_TEACHER) {
-    a = tgt;
-  } else if (mode == HAMT_POLICY_ARGMAX) {
-    int first = V;                                          // lowest index among the maxima (torch.max's tie rule on one device)
-#pragma unroll
-    for (int k = kCols - 1; k >= 0; --k) {
-      const int v = lane + 64 * k;
-      if (v < V && xm[k] == m1) first = v;
-    }
-    a = wave_min_i(first);
-    if (a >= V) a = 0;
-  } else {
-    float u;
-    if (uniform) {
-      u = uniform[b];
-    } else {                                                // counter hash of (seed, epoch, call_id, row): 24-bit uniform in [0, 1)
-      const RngKey key = rng_key(rng, call_id);
-      uint32_t h = hamt_mix32((uint32_t)b ^ key.k0);
-      h = hamt_mix32(h + key.k1);
-      u = (float)(h >> 8) * (1.0f / 16777216.0f);
-    }
-    // inverse CDF: the first slot of non-zero probability whose inclusive cumulative probability exceeds u (the fp32 wave scan is not
-    // guaranteed monotone to the last bit: a slot of probability 0 is never taken, whatever its rounded sum says); none: the last such slot
-    const float inv_s = dead ? 0.f : 1.0f / s1;
-    float base = 0.f;
-    int first = 0x7fffffff, last = -1;
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) {
-      if (64 * k < V) {                                     // (wave-uniform)
-        const int v = lane + 64 * k;
-        const float e = exp_rel(xm[k], m1);
-        float scan = e;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const float up = __shfl_up(scan, o, 64);
-          if (lane >= o) scan += up;
-        }
-        if (e > 0.f) {
-          last = v;
-          if (first == 0x7fffffff && (base + scan) * inv_s > u) first = v;
-        }
-        base += __shfl(scan, 63, 64);
-      }
-    }
-    first = wave_min_i(first);
-    last = wave_max_i(last);
-    a = first != 0x7fffffff ? first : last;
-    if (a < 0) a = 0;
-  }
+  const long long a = choose_action(mode, forced, tgt, xm, V, m1, s1, dead, uniform, rng, call_id, b, lane);
 
   // ---- log pi(a_t), entropy
   const bool a_ok = a >= 0 && a < V;
@@ -148,35 +229,19 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_fwd_kernel(
   if (a_ok) xa = (mr && mr[a]) ? -INFINITY : xr[a];
   bool live;
   const float lp = chosen_logp(mode, xa, lse1, a_ok, live);
-  float H = 0.f;
-  if (mode == HAMT_POLICY_SAMPLE) {
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) {
-      const float p = exp_rel(xm[k], lse1);
-      if (p > 0.f) H -= p * (xm[k] - lse1);                  // 0 log 0 = 0
-    }
-    H = wave_sum(H);
-    if (dead) H = 0.f;
-  }
+  const float H = mode == HAMT_POLICY_SAMPLE ? row_entropy(xm, lse1, dead) : 0.f;
 
-  // ---- environment action, previous-action angle, book-keeping
+  // ---- environment action (STOP is slot cand_len - 1 here; REVERIE's is column V), previous-action angle, book-keeping
   const bool was_ended = ended[b] != 0;
   const int cl = cand_len[b];
   int env = -1;
   if (a_ok && !dead && !was_ended && a != ignoreid && a != (long long)cl - 1) env = (int)a;
-  if (prev_angle) {
-    for (int j = lane; j < A; j += 64)
-      prev_angle[(size_t)b * A + j] = (env >= 0 && ob_ang) ? ob_ang[((size_t)b * V + env) * A + j] : 0.f;
-  }
-  if (lane == 0) {
-    ml[b] = ml_b;
-    action[b] = (int64_t)a;
-    logp[b] = lp;
-    if (mode == HAMT_POLICY_SAMPLE && ent) ent[b] = H;
-    mask[b] = was_ended ? 0.f : 1.f;
-    env_action[b] = env;
-    ended[b] = (was_ended || env < 0) ? 1 : 0;
-    if (hist_len && !was_ended) hist_len[b] += 1;
+  store_step(b, lane, V, A, mode, was_ended, env,           // the row, the shapes, the state before the step, the move
+             ml_b, a, lp, H,                                // the values, in the order of their destinations two lines down
+             ob_ang, prev_angle,                            // the angle feature: from, to
+             ml, action, logp, ent,                         // the destinations of the values
+             mask, env_action, ended, hist_len);            // derived from was_ended and env
+  if (lane == 0) {                                          // (2 floats per row; REVERIE keeps 3)
     lse[2 * b] = lse0;
     lse[2 * b + 1] = lse1;
   }
@@ -199,31 +264,16 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_step_bwd_kernel(
   const bool a_ok = a >= 0 && a < V;
   float xa = -INFINITY;
   if (a_ok) xa = (mr && mr[a]) ? -INFINITY : xr[a];
-  bool live;
-  chosen_logp(mode, xa, lse1, a_ok, live);
-  const bool dead = lse1 == -INFINITY;
+  const PolicyGrad g = policy_grad_row(mode, xm, xa, a_ok, lse1, b, g_logp, g_ent, gs_logp, gs_ent);
   const float gm = (g_ml && tgt != ignoreid) ? g_ml[(size_t)b * gs_ml] : 0.f;
   const float bad = (tgt != ignoreid && !(tgt >= 0 && tgt < V)) ? __builtin_nanf("") : 0.f;
-  const float gl = (g_logp && live && mode != HAMT_POLICY_TEACHER) ? g_logp[(size_t)b * gs_logp] : 0.f;
-  const bool with_ent = g_ent && mode == HAMT_POLICY_SAMPLE && !dead;
-  const float ge = with_ent ? g_ent[(size_t)b * gs_ent] : 0.f;
-  float p1[kCols], H = 0.f;
-#pragma unroll
-  for (int k = 0; k < kCols; ++k) {
-    p1[k] = dead ? 0.f : exp_rel(xm[k], lse1);
-    if (p1[k] > 0.f) H -= p1[k] * (xm[k] - lse1);
-  }
-  if (with_ent) H = wave_sum(H);                            // (wave-uniform condition)
 #pragma unroll
   for (int k = 0; k < kCols; ++k) {
     const int v = lane + 64 * k;
     if (v < V) {
-      float d = 0.f;
+      float d = 0.f;                                        // the cross-entropy term is taken on the UNMASKED row here
       if (tgt != ignoreid) d = gm * (exp_rel(x[k], lse0) - (v == tgt ? 1.f : 0.f)) + bad;
-      if (xm[k] != -INFINITY) {                             // masked (and -inf) positions take nothing from the last two terms
-        if (gl != 0.f) d += gl * ((v == a ? 1.f : 0.f) - p1[k]);
-        if (with_ent && p1[k] > 0.f) d += ge * (-p1[k] * ((xm[k] - lse1) + H));
-      }
+      if (xm[k] != -INFINITY) d = g.add(d, k, xm[k], v == a);   // masked (and -inf) positions take nothing from the policy terms
       dlogit[(size_t)b * ldd + v] = d;
     }
   }
@@ -263,30 +313,16 @@ extern "C" int hamt_policy_step_bwd(int B, int V, int mode, int64_t ignoreid, co
   return HAMT_OK;
 }
 
-// REVERIE's step (finetune_src/reverie/agent.py:253-307): the action row has ONE more column, V = ob_img_max_len, that stands for STOP and
-// is made from the object logits (:253-254) -- the best object's INDEX as the reference writes it, or its value (`stop_logit`); the
-// imitation cross-entropy is taken AFTER the back-track mask (:269 precedes :274); a second cross-entropy grounds the object (:275); STOP
-// is a_t >= V (:306), not slot cand_len - 1; a step that stops, or the rollout's last one, predicts the object (:299-304).  Same shape
-// as above: one wave per row, the V + 1 <= 256 action columns and the O <= 256 object columns 4 per lane in registers.
+// ---------------------------------------------------------------------------------------------------- 3. REVERIE's step
+// The action row has ONE more column, V = ob_img_max_len, that stands for STOP and is made from the object logits
+// (finetune_src/reverie/agent.py:253-254) -- the best object's INDEX as the reference writes it, or its value (`stop_logit`); the imitation
+// cross-entropy is taken AFTER the back-track mask (:269 precedes :274); a second cross-entropy grounds the object (:275); STOP is
+// a_t >= V (:306), not slot cand_len - 1; a step that stops, or the rollout's last one, predicts the object (:299-304).  The V + 1 <= 256
+// action columns and the O <= 256 object columns lie 4 per lane in registers, and the row core of part 1 runs on V + 1 columns.
 namespace {
 
 constexpr int kSavedInts = 3;            // per row: obj arg-max, effective ref target, effective action target (kIgnored / kBadTarget)
 constexpr int kIgnored = -1, kBadTarget = -2;
-
-// lowest index among the columns c < n whose value equals the wave's maximum over them (torch.max's tie rule); n <= 0: -1
-__device__ __forceinline__ int row_argmax(const float (&x)[kCols], int n, int lane) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int k = 0; k < kCols; ++k)
-    if (lane + 64 * k < n) m = fmaxf(m, x[k]);
-  m = wave_max(m);
-  int first = 0x7fffffff;
-#pragma unroll
-  for (int k = kCols - 1; k >= 0; --k)
-    if (lane + 64 * k < n && x[k] == m) first = lane + 64 * k;
-  first = wave_min_i(first);
-  return first == 0x7fffffff ? (n > 0 ? 0 : -1) : first;
-}
 
 // the masked action row of V + 1 columns: act_logit, then the STOP column
 __device__ __forceinline__ void load_ref_row(const float* __restrict__ xr, const uint8_t* __restrict__ mr, int V, float stop, int lane,
@@ -336,7 +372,7 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_ref_fwd_kernel(
   const int best_true = row_argmax(xo, ol, lane);
   const float stop = stop_logit == HAMT_STOP_LOGIT_VALUE ? mo : (float)best;
 
-  // ---- the action row of V + 1 columns, back-track-masked BEFORE the imitation cross-entropy (:269, :274)
+  // ---- the action row of V + 1 columns, back-track-masked BEFORE the imitation cross-entropy (:269, :274; the other agents mask after it)
   float xm[kCols];
   load_ref_row(xr, mr, V, stop, lane, xm);
   float m1, s1;
@@ -360,14 +396,14 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_ref_fwd_kernel(
     rt = (long long)ref_target[b];
   } else if (obj_id && goal_obj && tgt == V && !was_ended) {
     const int goal = goal_obj[b];
-    int first = 0x7fffffff;
+    int first = kNone;
 #pragma unroll
     for (int k = kCols - 1; k >= 0; --k) {
       const int c = lane + 64 * k;
       if (c < ol && obj_id[(size_t)b * O + c] == goal) first = c;
     }
     first = wave_min_i(first);
-    if (first != 0x7fffffff) rt = first;
+    if (first != kNone) rt = first;
   }
   int rt_s = kIgnored;
   float ref_b = 0.f;
@@ -377,84 +413,25 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_ref_fwd_kernel(
     ref_b = ok ? lse_o - orow[rt] : __builtin_nanf("");
   }
 
-  long long a;
-  if (forced) {
-    a = (long long)forced[b];
-  } else if (mode == HAMT_POLICY_TEACHER) {
-    a = tgt;
-  } else if (mode == HAMT_POLICY_ARGMAX) {
-    a = row_argmax(xm, Vp, lane);                           // (a dead row: every column equals the maximum -inf, slot 0)
-  } else {
-    float u;
-    if (uniform) {
-      u = uniform[b];
-    } else {                                                // the draw of policy_step_fwd_kernel
-      const RngKey key = rng_key(rng, call_id);
-      uint32_t h = hamt_mix32((uint32_t)b ^ key.k0);
-      h = hamt_mix32(h + key.k1);
-      u = (float)(h >> 8) * (1.0f / 16777216.0f);
-    }
-    // inverse CDF as in policy_step_fwd_kernel: the first slot of non-zero probability whose inclusive cumulative probability exceeds u
-    const float inv_s = dead ? 0.f : 1.0f / s1;
-    float base = 0.f;
-    int first = 0x7fffffff, last = -1;
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) {
-      if (64 * k < Vp) {                                    // (wave-uniform)
-        const int v = lane + 64 * k;
-        const float e = exp_rel(xm[k], m1);
-        float scan = e;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const float up = __shfl_up(scan, o, 64);
-          if (lane >= o) scan += up;
-        }
-        if (e > 0.f) {
-          last = v;
-          if (first == 0x7fffffff && (base + scan) * inv_s > u) first = v;
-        }
-        base += __shfl(scan, 63, 64);
-      }
-    }
-    first = wave_min_i(first);
-    last = wave_max_i(last);
-    a = first != 0x7fffffff ? first : last;
-    if (a < 0) a = 0;
-  }
+  const long long a = choose_action(mode, forced, tgt, xm, Vp, m1, s1, dead, uniform, rng, call_id, b, lane);
 
   // ---- log pi(a_t), entropy
   const bool a_ok = a >= 0 && a < Vp;
   const float xa = a_ok ? ref_row_at(xr, mr, V, stop, a) : -INFINITY;
   bool live;
   const float lp = chosen_logp(mode, xa, lse1, a_ok, live);
-  float H = 0.f;
-  if (mode == HAMT_POLICY_SAMPLE) {
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) {
-      const float p = exp_rel(xm[k], lse1);
-      if (p > 0.f) H -= p * (xm[k] - lse1);                  // 0 log 0 = 0
-    }
-    H = wave_sum(H);
-    if (dead) H = 0.f;
-  }
+  const float H = mode == HAMT_POLICY_SAMPLE ? row_entropy(xm, lse1, dead) : 0.f;
 
-  // ---- environment action (:306-307), previous-action angle, predicted object (:299-304), book-keeping
+  // ---- environment action (:306-307: STOP is a_t >= V, no cand_len - 1 rule), previous-action angle, book-keeping
   int env = -1;
   if (a >= 0 && a < V && !dead && !was_ended && a != ignoreid) env = (int)a;
-  if (prev_angle) {
-    for (int j = lane; j < A; j += 64)
-      prev_angle[(size_t)b * A + j] = (env >= 0 && ob_ang) ? ob_ang[((size_t)b * V + env) * A + j] : 0.f;
-  }
-  if (lane == 0) {
-    ml[b] = ml_b;
+  store_step(b, lane, V, A, mode, was_ended, env,           // the row, the shapes, the state before the step, the move
+             ml_b, a, lp, H,                                // the values, in the order of their destinations two lines down
+             ob_ang, prev_angle,                            // the angle feature: from, to
+             ml, action, logp, ent,                         // the destinations of the values
+             mask, env_action, ended, hist_len);            // derived from was_ended and env
+  if (lane == 0) {                                          // ---- what only this agent keeps: ref loss, predicted object (:299-304), 3 + 3 saved
     ref[b] = ref_b;
-    action[b] = (int64_t)a;
-    logp[b] = lp;
-    if (mode == HAMT_POLICY_SAMPLE && ent) ent[b] = H;
-    mask[b] = was_ended ? 0.f : 1.f;
-    env_action[b] = env;
-    ended[b] = (was_ended || env < 0) ? 1 : 0;
-    if (hist_len && !was_ended) hist_len[b] += 1;
     if ((a >= V || last_step) && !was_ended) {              // just stopped, or stopped by the step limit; no object in view: None
       if (pred_obj) pred_obj[b] = best_true;
       if (pred_obj_id) pred_obj_id[b] = (best_true >= 0 && obj_id) ? obj_id[(size_t)b * O + best_true] : -1;
@@ -487,21 +464,9 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_ref_bwd_kernel(
   const long long a = (long long)action[b];
   const bool a_ok = a >= 0 && a < Vp;
   const float xa = a_ok ? ref_row_at(xr, mr, V, stop, a) : -INFINITY;
-  bool live;
-  chosen_logp(mode, xa, lse1, a_ok, live);
-  const bool dead = lse1 == -INFINITY;
+  const PolicyGrad g = policy_grad_row(mode, xm, xa, a_ok, lse1, b, g_logp, g_ent, gs_logp, gs_ent);
   const float gm = (g_ml && tgt != kIgnored) ? g_ml[(size_t)b * gs_ml] : 0.f;
   const float bad = tgt == kBadTarget ? __builtin_nanf("") : 0.f;
-  const float gl = (g_logp && live && mode != HAMT_POLICY_TEACHER) ? g_logp[(size_t)b * gs_logp] : 0.f;
-  const bool with_ent = g_ent && mode == HAMT_POLICY_SAMPLE && !dead;
-  const float ge = with_ent ? g_ent[(size_t)b * gs_ent] : 0.f;
-  float p1[kCols], H = 0.f;
-#pragma unroll
-  for (int k = 0; k < kCols; ++k) {
-    p1[k] = dead ? 0.f : exp_rel(xm[k], lse1);
-    if (p1[k] > 0.f) H -= p1[k] * (xm[k] - lse1);
-  }
-  if (with_ent) H = wave_sum(H);                            // (wave-uniform condition)
   float d_stop = 0.f;                                       // column V's gradient: it lies in exactly one lane
 #pragma unroll
   for (int k = 0; k < kCols; ++k) {
@@ -509,9 +474,8 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void policy_ref_bwd_kernel(
     if (v < Vp) {
       float d = 0.f;
       if (xm[k] != -INFINITY) {                             // masked (and -inf) positions take nothing: the cross-entropy follows the mask here
-        if (tgt != kIgnored) d = gm * (p1[k] - (v == tgt ? 1.f : 0.f)) + bad;
-        if (gl != 0.f) d += gl * ((v == a ? 1.f : 0.f) - p1[k]);
-        if (with_ent && p1[k] > 0.f) d += ge * (-p1[k] * ((xm[k] - lse1) + H));
+        if (tgt != kIgnored) d = gm * (g.p[k] - (v == tgt ? 1.f : 0.f)) + bad;
+        d = g.add(d, k, xm[k], v == a);
       }
       if (v < V) dact[(size_t)b * ld_dact + v] = d;
       else d_stop = d;

@@ -1345,22 +1345,41 @@ def a2c_loss(logp, value, reward, mask, last_value=None, entropy=None, gamma=0.9
 POLICY_MODES = {"teacher": 0, "argmax": 1, "sample": 2}      # HAMT_POLICY_*
 
 
+def _fp32_rows(logit):
+    """a [B, V] logit as the step kernels read it: detached, fp32, unit column stride (no copy when it already is)"""
+    x = logit.detach()
+    return x if x.dtype == torch.float32 and x.stride(1) == 1 else x.to(torch.float32).contiguous()
+
+
+def _check_step_args(op_name, dev, specs):
+    """every (name, tensor or None, dtype, shape) of `specs`: a contiguous tensor of that dtype and shape on `dev`"""
+    for name, t_, dt, shape in specs:
+        if t_ is not None and (t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous() or t_.device != dev):
+            raise L.HamtError(f"{op_name}: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+
+
+def _grad_arg(g):
+    """a [B] gradient with element stride 1 or 0 (the expanded gradient of a plain sum) goes in as it is: no copy kernel"""
+    if g is None:
+        return None, 0
+    if g.dtype != torch.float32 or g.stride(0) not in (0, 1):
+        g = g.to(torch.float32).contiguous()
+    return g, g.stride(0)
+
+
 class PolicyStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logit, target, bt_mask, cand_len, ended, mask, ob_ang, hist_len, forced_action, uniform, mode, ignoreid, call_id, out):
         _chk(logit, "policy_step")
-        x = logit.detach()
-        if x.dtype != torch.float32 or x.stride(1) != 1:
-            x = x.to(torch.float32).contiguous()
+        x = _fp32_rows(logit)
         B, V = x.shape
         dev = x.device
         A = 0 if ob_ang is None else ob_ang.shape[-1]
-        for name, t_, dt, shape in (("target", target, torch.int64, (B,)), ("bt_mask", bt_mask, torch.uint8, (B, V)), ("cand_len", cand_len, torch.int32, (B,)),
-                                    ("ended", ended, torch.uint8, (B,)), ("mask", mask, torch.float32, (B,)), ("ob_ang", ob_ang, torch.float32, (B, V, A)),
-                                    ("hist_len", hist_len, torch.int32, (B,)), ("forced_action", forced_action, torch.int64, (B,)),
-                                    ("uniform", uniform, torch.float32, (B,))):
-            if t_ is not None and (t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous() or t_.device != dev):
-                raise L.HamtError(f"policy_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+        _check_step_args("policy_step", dev, (
+            ("target", target, torch.int64, (B,)), ("bt_mask", bt_mask, torch.uint8, (B, V)), ("cand_len", cand_len, torch.int32, (B,)),
+            ("ended", ended, torch.uint8, (B,)), ("mask", mask, torch.float32, (B,)), ("ob_ang", ob_ang, torch.float32, (B, V, A)),
+            ("hist_len", hist_len, torch.int32, (B,)), ("forced_action", forced_action, torch.int64, (B,)),
+            ("uniform", uniform, torch.float32, (B,))))
         ml, logp, ent = out if out is not None else (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
         action = torch.empty(B, dtype=torch.int64, device=dev)
         env_action = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1383,13 +1402,7 @@ class PolicyStepFn(torch.autograd.Function):
         x, target, bt_mask, action, lse = ctx.saved_tensors
         mode, ignoreid = ctx.meta
         B, V = x.shape
-        def f(g):          # [B] with element stride 1 or 0 (the expanded gradient of a plain sum) goes in as it is: no copy kernel
-            if g is None:
-                return None, 0
-            if g.dtype != torch.float32 or g.stride(0) not in (0, 1):
-                g = g.to(torch.float32).contiguous()
-            return g, g.stride(0)
-        (g_ml, s_ml), (g_logp, s_logp), (g_ent, s_ent) = f(g_ml), f(g_logp), f(g_ent)
+        (g_ml, s_ml), (g_logp, s_logp), (g_ent, s_ent) = _grad_arg(g_ml), _grad_arg(g_logp), _grad_arg(g_ent)
         dx = torch.empty(B, V, dtype=torch.float32, device=x.device)
         L.check(L.load().hamt_policy_step_bwd(B, V, mode, ignoreid, _p(x), x.stride(0), _p(target), _p(bt_mask), _p(action), _p(lse), _p(g_ml),
                                               _p(g_logp), _p(g_ent), s_ml, s_logp, s_ent, _p(dx), V, _stream()), "hamt_policy_step_bwd")
@@ -1415,15 +1428,6 @@ def policy_step(logit, cand_len, ended, mask, mode="sample", target=None, bt_mas
 STOP_LOGITS = {"index": 0, "value": 1}                       # HAMT_STOP_LOGIT_*
 
 
-def _grad_arg(g):
-    """a [B] gradient with element stride 1 or 0 (the expanded gradient of a plain sum) goes in as it is: no copy kernel"""
-    if g is None:
-        return None, 0
-    if g.dtype != torch.float32 or g.stride(0) not in (0, 1):
-        g = g.to(torch.float32).contiguous()
-    return g, g.stride(0)
-
-
 class PolicyRefStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, act_logit, obj_logit, obj_len, cand_len, ended, mask, target, ref_target, obj_id, goal_obj, bt_mask, ob_ang, hist_len,
@@ -1432,23 +1436,17 @@ class PolicyRefStepFn(torch.autograd.Function):
         if act_logit.dim() != 2 or obj_logit.dim() != 2 or obj_logit.shape[0] != act_logit.shape[0] or obj_logit.device != act_logit.device:
             raise L.HamtError(f"policy_ref_step: act_logit [B, V] and obj_logit [B, O] on one device, got {tuple(act_logit.shape)} on "
                               f"{act_logit.device} and {tuple(obj_logit.shape)} on {obj_logit.device}")
-        x, xo = act_logit.detach(), obj_logit.detach()
-        if x.dtype != torch.float32 or x.stride(1) != 1:
-            x = x.to(torch.float32).contiguous()
-        if xo.dtype != torch.float32 or xo.stride(1) != 1:
-            xo = xo.to(torch.float32).contiguous()
+        x, xo = _fp32_rows(act_logit), _fp32_rows(obj_logit)
         (B, V), O = x.shape, xo.shape[1]
         dev = x.device
         A = 0 if ob_ang is None else ob_ang.shape[-1]
         i32_, i64_, u8_, f32_ = torch.int32, torch.int64, torch.uint8, torch.float32
-        for name, t_, dt, shape in (("obj_len", obj_len, i32_, (B,)), ("cand_len", cand_len, i32_, (B,)), ("ended", ended, u8_, (B,)),
-                                    ("mask", mask, f32_, (B,)), ("target", target, i64_, (B,)), ("ref_target", ref_target, i64_, (B,)),
-                                    ("obj_id", obj_id, i32_, (B, O)), ("goal_obj", goal_obj, i32_, (B,)), ("bt_mask", bt_mask, u8_, (B, V)),
-                                    ("ob_ang", ob_ang, f32_, (B, V, A)), ("hist_len", hist_len, i32_, (B,)),
-                                    ("forced_action", forced_action, i64_, (B,)), ("uniform", uniform, f32_, (B,)),
-                                    ("pred_obj", pred_obj, i32_, (B,)), ("pred_obj_id", pred_obj_id, i32_, (B,))):
-            if t_ is not None and (t_.dtype != dt or tuple(t_.shape) != shape or not t_.is_contiguous() or t_.device != dev):
-                raise L.HamtError(f"policy_ref_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}, got {t_.dtype} {tuple(t_.shape)} on {t_.device}")
+        _check_step_args("policy_ref_step", dev, (
+            ("obj_len", obj_len, i32_, (B,)), ("cand_len", cand_len, i32_, (B,)), ("ended", ended, u8_, (B,)), ("mask", mask, f32_, (B,)),
+            ("target", target, i64_, (B,)), ("ref_target", ref_target, i64_, (B,)), ("obj_id", obj_id, i32_, (B, O)),
+            ("goal_obj", goal_obj, i32_, (B,)), ("bt_mask", bt_mask, u8_, (B, V)), ("ob_ang", ob_ang, f32_, (B, V, A)),
+            ("hist_len", hist_len, i32_, (B,)), ("forced_action", forced_action, i64_, (B,)), ("uniform", uniform, f32_, (B,)),
+            ("pred_obj", pred_obj, i32_, (B,)), ("pred_obj_id", pred_obj_id, i32_, (B,))))
         if (obj_id is None) != (goal_obj is None) and ref_target is None:
             raise L.HamtError("policy_ref_step: the object target comes from ref_target, or from obj_id AND goal_obj")
         ml, ref, logp, ent = out if out is not None else (torch.empty(B, dtype=f32_, device=dev) for _ in range(4))
