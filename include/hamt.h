@@ -405,7 +405,8 @@ int hamt_mean_mid_bwd(int B, int S, int H, const float* dy, float* dx, void* str
 int hamt_mul_bcast_fwd(int B, int S, int H, const float* a, const float* c, int ldc_rows, float* y, void* stream);
 int hamt_mul_bcast_bwd(int B, int S, int H, const float* a, const float* c, int ldc_rows, const float* dy,
                        float* da, float* dc, void* stream);
-/* sums x[B,S,H] over b and/or s into out (accumulate): mode 0: out[H] += sum_{b,s}; 1: out[s,H] += sum_b */
+/* sums x[B,S,H] over b and/or s; `out` is ADDED to in both modes, never overwritten (zero it first for the plain sum):
+ * mode 0: out[H] += sum_{b,s} (ws: >= 64*H floats); 1: out[s,H] += sum_b */
 int hamt_sum_rows(int B, int S, int H, const float* x, int mode, float* out, float* ws, void* stream);
 
 /* elementwise: out = a + b (+ c) ; dropout forward/backward (feature dropout, model_HAMT.py:32-52) */

@@ -142,45 +142,45 @@ __global__ void a2c_bwd_kernel(size_t n, const float* __restrict__ ret, const fl
 }  // namespace
 
 extern "C" int hamt_ce_fwd(int R, int C, const float* x, int ldx, const int64_t* label, float* loss, float* lse, void* stream) {
-  HAMT_CHECK_ARG(x && label && loss && lse && C > 0, "hamt_ce_fwd: bad argument");
   if (R == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && label && loss && lse && C > 0, "hamt_ce_fwd: bad argument");
   hipLaunchKernelGGL(ce_fwd_kernel, dim3(R), dim3(256), 0, as_stream(stream), C, x, ldx, label, loss, lse);
   HAMT_CHECK_LAUNCH("hamt_ce_fwd");
   return HAMT_OK;
 }
 extern "C" int hamt_ce_bwd(int R, int C, const float* x, int ldx, const int64_t* label, const float* lse, const float* g,
                            float* dx, int lddx, void* stream) {
-  HAMT_CHECK_ARG(x && label && lse && g && dx, "hamt_ce_bwd: null pointer");
   if (R == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && label && lse && g && dx, "hamt_ce_bwd: null pointer");
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(R), dim3(256), 0, as_stream(stream), C, x, ldx, label, lse, g, dx, lddx);
   HAMT_CHECK_LAUNCH("hamt_ce_bwd");
   return HAMT_OK;
 }
 extern "C" int hamt_mse_fwd(size_t n, const float* x, const float* t, float* loss, void* stream) {
-  HAMT_CHECK_ARG(x && t && loss, "hamt_mse_fwd: null pointer");
   if (n == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && t && loss, "hamt_mse_fwd: null pointer");
   hipLaunchKernelGGL(mse_fwd_kernel, dim3(nb(n)), dim3(256), 0, as_stream(stream), n, x, t, loss);
   HAMT_CHECK_LAUNCH("hamt_mse_fwd");
   return HAMT_OK;
 }
 extern "C" int hamt_mse_bwd(size_t n, const float* x, const float* t, const float* g, float* dx, void* stream) {
-  HAMT_CHECK_ARG(x && t && g && dx, "hamt_mse_bwd: null pointer");
   if (n == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && t && g && dx, "hamt_mse_bwd: null pointer");
   hipLaunchKernelGGL(mse_bwd_kernel, dim3(nb(n)), dim3(256), 0, as_stream(stream), n, x, t, g, dx);
   HAMT_CHECK_LAUNCH("hamt_mse_bwd");
   return HAMT_OK;
 }
 extern "C" int hamt_kl_fwd(int R, int C, const float* x, int ldx, const float* t, int ldt, float* loss, float* lse, void* stream) {
-  HAMT_CHECK_ARG(x && t && loss && lse && C > 0, "hamt_kl_fwd: bad argument");
   if (R == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && t && loss && lse && C > 0, "hamt_kl_fwd: bad argument");
   hipLaunchKernelGGL(kl_fwd_kernel, dim3(R), dim3(256), 0, as_stream(stream), C, x, ldx, t, ldt, loss, lse);
   HAMT_CHECK_LAUNCH("hamt_kl_fwd");
   return HAMT_OK;
 }
 extern "C" int hamt_kl_bwd(int R, int C, const float* x, int ldx, const float* t, int ldt, const float* lse, const float* g,
                            float* dx, int lddx, void* stream) {
-  HAMT_CHECK_ARG(x && t && lse && g && dx, "hamt_kl_bwd: null pointer");
   if (R == 0) return HAMT_OK;
+  HAMT_CHECK_ARG(x && t && lse && g && dx, "hamt_kl_bwd: null pointer");
   hipLaunchKernelGGL(kl_bwd_kernel, dim3(R), dim3(256), 0, as_stream(stream), C, x, ldx, t, ldt, lse, g, dx, lddx);
   HAMT_CHECK_LAUNCH("hamt_kl_bwd");
   return HAMT_OK;
