@@ -494,6 +494,20 @@ int hamt_mse_bwd(size_t n, const float* x, const float* t, const float* g, float
 int hamt_kl_fwd(int R, int C, const float* x, int ldx, const float* t, int ldt, float* loss, float* lse, void* stream);
 int hamt_kl_bwd(int R, int C, const float* x, int ldx, const float* t, int ldt, const float* lse,
                 const float* g, float* dx, int lddx, void* stream);
+/* The loss / accuracy side of the proxy-task validation pass (pretrain_src/main_r2r.py:344-511), accumulated on the device.  Each call
+ * ADDS into caller-owned accumulators -- sums fp64 [4], counts int64 [4] -- and reads nothing from the host; R == 0 is a no-op.  The
+ * row terms are fp32 exactly as hamt_ce_fwd / hamt_kl_fwd / hamt_mse_fwd compute them; one workgroup folds them in fp64 in a fixed
+ * order (no floating-point atomics), so the totals are bit-identical from run to run.  ws: 2 R floats of scratch, fully rewritten.
+ *   hamt_eval_ce        sums[0] += sum of logsumexp(x[r]) - x[r, label[r]], counts[0] += rows whose arg-max (the LOWEST index among
+ *                       the maxima, scores.max(-1)[1]) equals the label, counts[1] += rows, over the rows with label >= 0 (a negative
+ *                       label: the row is ignored altogether; a label >= C: NaN).  A row with a NaN logit adds NaN and is not correct.
+ *   hamt_eval_kl        sums[0] += sum_r sum_c t (log t - log_softmax(x)) with 0 log 0 = 0, counts[0] += rows where argmax x[r] ==
+ *                       argmax t[r] (lowest index on ties), counts[1] += R
+ *   hamt_eval_mse_cols  sums[c] += sum_r (x[r,c] - t[r,c])^2 for c < C <= 4; one launch */
+int hamt_eval_ce(int R, int C, const float* x, int ldx, const int64_t* label, float* ws, double* sums, int64_t* counts, void* stream);
+int hamt_eval_kl(int R, int C, const float* x, int ldx, const float* t, int ldt, float* ws, double* sums, int64_t* counts,
+                 void* stream);
+int hamt_eval_mse_cols(int R, int C, const float* x, int ldx, const float* t, int ldt, double* sums, void* stream);
 /* A2C rollout loss of the finetune agent (finetune_src/r2r/agent_cmt.py:476-518), all [T, B] steps x episodes at once
  * (row-major [T][B] fp32 arrays): ret[t,b] = discounted return R_t = gamma R_{t+1} + reward_t seeded with last_value[b]
  * (NULL = 0: the caller passes the critic's value of the last state for episodes that have not ended, 0 for the others);

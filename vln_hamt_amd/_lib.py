@@ -151,6 +151,9 @@ SIGNATURES = {
     "hamt_mse_bwd": [sz, vp, vp, vp, vp, vp],
     "hamt_kl_fwd": [i32, i32, vp, i32, vp, i32, vp, vp, vp],
     "hamt_kl_bwd": [i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp],
+    "hamt_eval_ce": [i32, i32, vp, i32, vp, vp, vp, vp, vp],
+    "hamt_eval_kl": [i32, i32, vp, i32, vp, i32, vp, vp, vp, vp],
+    "hamt_eval_mse_cols": [i32, i32, vp, i32, vp, i32, vp, vp],
     "hamt_extend_mask": [sz, vp, vp, vp],
     "hamt_debug_fill_lds": [u32, vp],
     "hamt_debug_wgrad_timing": [C.c_int],

@@ -1646,3 +1646,105 @@ def nav_eval_back(graphs, scan, path, path_len, gt, gt_len, midstop, gt_midstop)
 
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
+
+
+# ------------------------------------------------------------------------------------------ validation accumulators
+EVAL_SLOTS = 4              # double sums[4], int64 counts[4] (include/hamt.h: hamt_eval_*)
+
+
+class EvalAccumulator:
+    """The device totals of one validation pass: `sums` fp64 [4] and `counts` int64 [4] behind one 64-byte buffer, which eval_ce /
+    eval_kl / eval_mse_cols ADD into.  Nothing is read back until `read()`, the pass's one device-to-host copy."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.HamtError(f"EvalAccumulator: device is {self.device}; the HAMT kernels run on the GPU only (no CPU fallback)")
+        self.buf = torch.zeros(2 * EVAL_SLOTS, dtype=torch.int64, device=self.device)
+        self.device = self.buf.device       # ("cuda" -> the current device, with its index)
+        self.sums = self.buf[:EVAL_SLOTS].view(torch.float64)
+        self.counts = self.buf[EVAL_SLOTS:]
+        self._ws = None
+
+    def zero_(self):
+        self.buf.zero_()
+        return self
+
+    def workspace(self, R: int) -> torch.Tensor:
+        """2 R floats of scratch for the row kernels, grown geometrically and kept (every call rewrites what it reads)"""
+        if self._ws is None or self._ws.numel() < 2 * R:
+            self._ws = torch.empty(max(2 * R, 1024, 0 if self._ws is None else 2 * self._ws.numel()), dtype=torch.float32, device=self.device)
+        return self._ws
+
+    def read(self):
+        """(sums, counts) as lists of Python floats / ints: ONE device-to-host copy, which waits for the updates in front of it"""
+        host = self.buf.cpu()
+        return host[:EVAL_SLOTS].view(torch.float64).tolist(), host[EVAL_SLOTS:].tolist()
+
+
+def _eval_rows(op_name, x, name, dev, dtype=torch.float32):
+    """a [R, C] operand of the eval kernels: `dtype`, on `dev`, unit stride in the last dimension; its row stride goes in as ld"""
+    if x.dim() == 2 and x.dtype == dtype and x.device == dev and x.numel() == 0:        # (no rows: nothing is read, strides mean nothing)
+        return max(1, x.shape[1])
+    if x.dim() != 2 or x.dtype != dtype or x.device != dev or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise L.HamtError(f"{op_name}: {name} must be a 2-D {dtype} tensor on {dev} with a contiguous last dimension, got {x.dtype} "
+                          f"{tuple(x.shape)} strides {tuple(x.stride())} on {x.device}")
+    return _ld(x)
+
+
+def _eval_acc(op_name, acc, dev):
+    if not isinstance(acc, EvalAccumulator) or acc.device != dev:
+        raise L.HamtError(f"{op_name}: acc must be an ops.EvalAccumulator on {dev}")
+
+
+@torch.no_grad()
+def eval_ce(x, label, acc):
+    """acc.sums[0] += F.cross_entropy(x, label, reduction='sum') over the rows with label >= 0, acc.counts[0] += the rows among them whose
+    arg-max (lowest index on ties) is the label, acc.counts[1] += their number -- what validate_mlm / _sap / _itm keep per batch
+    (main_r2r.py:355-358).  x fp32 [R, C] with any row stride, label int64 [R].  Two launches, nothing read from the host."""
+    _chk(x, "eval_ce")
+    dev = x.device
+    ldx = _eval_rows("eval_ce", x, "x", dev)
+    R, Cc = x.shape
+    _check_step_args("eval_ce", dev, [("label", label, torch.int64, (R,))])
+    _eval_acc("eval_ce", acc, dev)
+    if R == 0 or Cc == 0:
+        return acc
+    L.check(L.load().hamt_eval_ce(R, Cc, _p(x), ldx, _p(label), _p(acc.workspace(R)), _p(acc.sums), _p(acc.counts), _stream()), "hamt_eval_ce")
+    return acc
+
+
+@torch.no_grad()
+def eval_kl(x, t, acc):
+    """acc.sums[0] += F.kl_div(log_softmax(x), t, reduction='sum'), acc.counts[0] += rows where argmax x == argmax t,
+    acc.counts[1] += R (validate_mrc, main_r2r.py:468-473).  x, t fp32 [R, C] with any row strides."""
+    _chk(x, "eval_kl")
+    dev = x.device
+    ldx = _eval_rows("eval_kl", x, "x", dev)
+    ldt = _eval_rows("eval_kl", t, "t", dev)
+    R, Cc = x.shape
+    if tuple(t.shape) != (R, Cc):
+        raise L.HamtError(f"eval_kl: t must have x's shape {(R, Cc)}, got {tuple(t.shape)}")
+    _eval_acc("eval_kl", acc, dev)
+    if R == 0 or Cc == 0:
+        return acc
+    L.check(L.load().hamt_eval_kl(R, Cc, _p(x), ldx, _p(t), ldt, _p(acc.workspace(R)), _p(acc.sums), _p(acc.counts), _stream()), "hamt_eval_kl")
+    return acc
+
+
+@torch.no_grad()
+def eval_mse_cols(x, t, acc):
+    """acc.sums[c] += F.mse_loss(x[:, c], t[:, c], reduction='sum') for the C <= 4 columns of x, t fp32 [R, C] (validate_sar /
+    validate_sprel, main_r2r.py:407-409, 437-438).  One launch."""
+    _chk(x, "eval_mse_cols")
+    dev = x.device
+    ldx = _eval_rows("eval_mse_cols", x, "x", dev)
+    ldt = _eval_rows("eval_mse_cols", t, "t", dev)
+    R, Cc = x.shape
+    if tuple(t.shape) != (R, Cc) or not 1 <= Cc <= EVAL_SLOTS:
+        raise L.HamtError(f"eval_mse_cols: x and t must share a shape [R, 1 <= C <= {EVAL_SLOTS}], got {tuple(x.shape)} and {tuple(t.shape)}")
+    _eval_acc("eval_mse_cols", acc, dev)
+    if R == 0:
+        return acc
+    L.check(L.load().hamt_eval_mse_cols(R, Cc, _p(x), ldx, _p(t), ldt, _p(acc.sums), _stream()), "hamt_eval_mse_cols")
+    return acc
