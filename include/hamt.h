@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 #define HAMT_ABI_VERSION 2   /* 2 (round 6): hamt_gemm_ln_fwd / hamt_graph_split_* removed (round 5); hamt_embed_sum_bwd takes V and ws_bytes,
-                              * hamt_scatter_add_rows_ordered takes T; hamt_wgrad_grouped_ex and the dtype HAMT_F16 added */
+                              * hamt_scatter_add_rows_ordered takes T; hamt_wgrad_grouped_ex and the dtype HAMT_F16 added.  Entry points added since (the
+                              * policy / nav / eval families, hamt_attn_cls_fwd) change no existing signature and leave the number at 2. */
 
 typedef enum { HAMT_OK = 0, HAMT_ERR_ARG = -1, HAMT_ERR_UNSUPPORTED = -2, HAMT_ERR_LAUNCH = -3 } hamt_status;
 typedef enum { HAMT_F32 = 0, HAMT_BF16 = 1,
@@ -213,6 +214,14 @@ int hamt_attn_small_fwd(const hamt_attn_desc* d, const void* q, const void* k, c
 int hamt_attn_small_bwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v,
                         const float* add_mask, const void* o, const void* d_o, const float* lse,
                         float* delta, void* dq, void* dk, void* dv, const uint64_t* rng, void* stream);
+
+/* attn_cls (csrc/attn_cls.hip): the same attention for ONE query per (image, head) -- the cls row of a ViT's last block in a forward-only
+ * pass that reads nothing but x[:, 0] afterwards (vision_transformer.py:346).  d->B images, d->Sq must be 1, d->Sk <= 256 keys per image
+ * (more: HAMT_ERR_UNSUPPORTED, nothing is launched), d_head 64, p_drop 0, no mask.  q row b at q + b*ldq, K / V rows (b*Sk + j), o row b at
+ * o + b*ldo ([B, heads*64]); q / k / v share dtype_qkv (fp32 or bf16), o has dtype_o; every base pointer and row 16-byte aligned.
+ * o = softmax(q k^T * scale) v with scores, softmax and the P V sums in fp32, whatever d->prec says.  One wave per (image, head), two
+ * streaming passes over K and V; no atomics, no scratch, no lse (there is no backward). */
+int hamt_attn_cls_fwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v, void* o, void* stream);
 
 /* Packed ("varlen") self-attention, bf16 path: the B sequences lie back to back, sample b owns rows [cu_seqlens[b], cu_seqlens[b + 1])
  * of q / k / v / o / d_o / dq / dk / dv (row strides as in the descriptor), at most d->Sq = d->Sk <= 128 tokens each, every key real (no

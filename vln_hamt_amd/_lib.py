@@ -110,6 +110,7 @@ SIGNATURES = {
     "hamt_colsum": [i32, i32, vp, i32, i32, vp, i32, vp, vp],
     "hamt_attn_small_fwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_attn_small_bwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "hamt_attn_cls_fwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp],
     "hamt_attn_varlen_fwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_attn_varlen_bwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "hamt_attn_varlen_cross_fwd": [C.POINTER(AttnDesc), vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp],

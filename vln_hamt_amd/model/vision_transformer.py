@@ -13,6 +13,11 @@ Same class surface and parameter names as the reference's ``VisionTransformer`` 
   fc2 -> residual add;
 * final LayerNorm, cls row.
 
+``num_classes > 0`` adds the classifier ``head`` (:296) as a parameter container: ``forward`` stays ``forward_features``, the feature
+extractor (``preprocess/extract.py``) applies the head itself.  ``forward_features(x, cls_tail=True)`` is the forward-only eval
+form: only the cls row leaves the last block, so that block projects K and V for all tokens and runs everything else -- Q, the
+attention (``hamt_attn_cls_fwd``), proj, the MLP, the final LayerNorm -- on the cls rows alone.
+
 bf16 mode with the branch dropouts off: one autograd Function per half block (``blocks_preln.py``: bf16 images between
 the kernels, residual adds in GEMM epilogues / in the LayerNorm-backward kernel, queued weight gradients).  Otherwise
 (fp32 mode, branch dropout on) the fine-grained Functions of ``ops.py``.  Every op has its backward, so images that need
@@ -139,11 +144,12 @@ class PatchEmbed(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """vision_transformer.py:226-362 without distillation token / classifier head (`num_classes=0`)."""
+    """vision_transformer.py:226-362 without distillation token; the classifier head (:296) only with `num_classes > 0`."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0,
-                 drop_rate=0.0, attn_drop_rate=0.0, hamt_precision="bf16"):
+                 drop_rate=0.0, attn_drop_rate=0.0, hamt_precision="bf16", num_classes=0):
         super().__init__()
+        self.num_classes = int(num_classes)
         self.num_features = self.embed_dim = embed_dim
         self.patch_embed = PatchEmbed(img_size, patch_size, in_chans, embed_dim, hamt_precision)
         n_tok = self.patch_embed.num_patches + 1
@@ -153,11 +159,55 @@ class VisionTransformer(nn.Module):
         self.blocks = nn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, drop_rate, attn_drop_rate, hamt_precision)
                                       for _ in range(depth)])
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
+        if self.num_classes > 0:
+            self.head = nn.Linear(embed_dim, self.num_classes)
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         nn.init.trunc_normal_(self.cls_token, std=0.02)
 
-    def forward_features(self, x):
-        """x: float images (B, 3, H, W), or a `PatchRows` holder (data/image_prep.py) standing for such a tensor"""
+    def _check_cls_tail(self):
+        """`cls_tail` drops every row but cls inside the last block: only a forward nobody differentiates, without dropout, may do that"""
+        blk = self.blocks[-1]
+        if self.training or blk.training or blk.attn.training or blk.mlp.training:
+            raise L.HamtError("forward_features(cls_tail=True): the model is in train() mode; the cls-only tail is an eval()-mode forward")
+        if torch.is_grad_enabled():
+            raise L.HamtError("forward_features(cls_tail=True): grad mode is on; the cls-only tail has no backward, call it under torch.no_grad()")
+        for name, d in (("attn.attn_drop", blk.attn.attn_drop), ("attn.proj_drop", blk.attn.proj_drop), ("mlp.drop", blk.mlp.drop)):
+            if d.training and d.p > 0.0:
+                raise L.HamtError(f"forward_features(cls_tail=True): dropout {name} (p = {d.p}) of the last block is active")
+
+    def _cls_tail(self, x):
+        """The last block and the final LayerNorm for the cls rows of x (B, S, D) -> (B, D).  K and V need every token (norm1 and the
+        [D:3D] rows of the fused qkv projection run on all of them); everything behind the attention reads the cls row only."""
+        blk = self.blocks[-1]
+        a, m = blk.attn, blk.mlp
+        B, S, D = x.shape
+        M, prec = B * S, a.prec
+        x2 = x.reshape(M, D)
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        # fp32 mode: the parameter itself; bf16 mode: its cached bf16 image.  Either is sliced by rows ((N, K) layout: contiguous), not copied.
+        wqkv, bqkv = ops.weight_operand(a.qkv.weight, prec), a.qkv.bias.detach()
+        if blocks_preln.usable(prec, x):
+            y = blocks_preln._ln16(x2, blk.norm1.weight.detach(), blk.norm1.bias.detach(), blk.norm1.eps)[0][:M]
+        else:
+            y = ops.layer_norm(x2, None, blk.norm1, want16=prec == "bf16")
+            y = ops.shadow16(y)[:M] if prec == "bf16" else y
+        kv = torch.empty(M, 2 * D, dtype=y.dtype, device=x.device)
+        ops.gemm(y, wqkv[D:], kv, bias=bqkv[D:], prec=prec)
+        xc = ops.gather_rows(x2, ops.const_index("arange_mul", B, S, device=x.device))          # the cls rows: query input and residual
+        yc = ops.layer_norm(xc, None, blk.norm1, want16=prec == "bf16")
+        q = torch.empty(B, D, dtype=y.dtype, device=x.device)
+        ops.gemm(ops.shadow16(yc)[:B] if prec == "bf16" else yc, wqkv[:D], q, bias=bqkv[:D], prec=prec)
+        ctx = ops.attn_cls(q, kv[:, :D], kv[:, D:], a.num_heads)
+        xc = ops.linear(ctx, a.proj.weight, a.proj.bias, ops.ACT_NONE, prec, residual=xc)
+        xc = m(ops.layer_norm(xc, None, blk.norm2, want16=True), residual=xc)
+        return ops.layer_norm(xc, None, self.norm)
+
+    def forward_features(self, x, cls_tail=False):
+        """x: float images (B, 3, H, W), or a `PatchRows` holder (data/image_prep.py) standing for such a tensor.
+        cls_tail: run the last block for the cls rows only (eval mode under torch.no_grad() with the last block's dropouts off;
+        anything else raises)."""
+        if cls_tail:
+            self._check_cls_tail()
         streams.gate(self.cls_token, self.pos_embed, self.norm)                      # (called as a method: no module hook in front)
         x = self.patch_embed(x)                                                      # (B, N, D)
         B, N, D = x.shape
@@ -165,6 +215,10 @@ class VisionTransformer(nn.Module):
         idx = torch.arange(N + 1, device=x.device).repeat(B)
         x = ops.gather_rows(self.pos_embed.view(N + 1, D), idx, base=x)             # x + pos_embed (:342)
         x = ops.dropout(x, float(self.pos_drop.p), self.training).view(B, N + 1, D)
+        if cls_tail:
+            for blk in list(self.blocks)[:-1]:
+                x = blk(x)
+            return self._cls_tail(x)
         x = self.blocks(x)
         x = ops.layer_norm(x, None, self.norm)
         return x[:, 0]
@@ -174,5 +228,5 @@ class VisionTransformer(nn.Module):
 
 
 def vit_base_patch16_224(**kw):
-    """ViT-B/16 (vision_transformer.py:486-493) without classifier head."""
+    """ViT-B/16 (vision_transformer.py:486-493); without classifier head unless `num_classes` is given."""
     return VisionTransformer(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, **kw)

@@ -540,6 +540,23 @@ def attention(q_src, kv_src, add_mask, B, heads, p_drop, prec="fp32"):
     return AttnFn.apply(q_src, kv_src, add_mask, B, heads, p_drop, prec)
 
 
+def attn_cls(q, k, v, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(64)) v for ONE query per (image, head): q [n, heads*64], k / v [n*Sk, heads*64] (2-D views with unit inner
+    stride, e.g. column blocks of a packed [k|v] buffer; fp32 or bf16, one dtype for the three) -> fp32 [n, heads*64].  Forward only
+    (`hamt_attn_cls_fwd` keeps no log-sum-exp): refuses to run where autograd would record it."""
+    _chk(q, "attn_cls")
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        raise L.HamtError("attn_cls: forward-only kernel (no backward); call it under torch.no_grad()")
+    n, H = q.shape
+    if H != heads * 64 or k.shape[1] != H or v.shape != k.shape or n == 0 or k.shape[0] % n or not (q.dtype == k.dtype == v.dtype):
+        raise L.HamtError(f"attn_cls: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, v {tuple(v.shape)} {v.dtype}, heads {heads}")
+    Sk = k.shape[0] // n
+    out = torch.empty(n, H, dtype=torch.float32, device=q.device)
+    d = L.AttnDesc(n, heads, 1, Sk, 64, _ld(q), _ld(k), _ld(v), H, _dt(q), L.HAMT_F32, 1.0 / math.sqrt(64), 0.0, 0, L.PREC_F32)
+    L.check(L.load().hamt_attn_cls_fwd(C.byref(d), _p(q), _p(k), _p(v), _p(out), _stream()), "hamt_attn_cls_fwd")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ LayerNorm family
 def shadow16(x: torch.Tensor):
     """bf16 image [Mpad64, H] of an activation tensor if its producer emitted one (LayerNorm kernels do), else None."""
