@@ -33,7 +33,7 @@ extern "C" {
 
 #define HAMT_ABI_VERSION 2   /* 2 (round 6): hamt_gemm_ln_fwd / hamt_graph_split_* removed (round 5); hamt_embed_sum_bwd takes V and ws_bytes,
                               * hamt_scatter_add_rows_ordered takes T; hamt_wgrad_grouped_ex and the dtype HAMT_F16 added.  Entry points added since (the
-                              * policy / nav / eval families, hamt_attn_cls_fwd) change no existing signature and leave the number at 2. */
+                              * policy / nav / eval families, hamt_attn_cls_fwd, hamt_image_resample) change no existing signature and leave the number at 2. */
 
 typedef enum { HAMT_OK = 0, HAMT_ERR_ARG = -1, HAMT_ERR_UNSUPPORTED = -2, HAMT_ERR_LAUNCH = -3 } hamt_status;
 typedef enum { HAMT_F32 = 0, HAMT_BF16 = 1,
@@ -454,6 +454,33 @@ typedef struct {
 } hamt_image_prep_desc;
 int hamt_image_prep(const hamt_image_prep_desc* d, const hamt_image_view* views_host, const hamt_image_view* views_dev,
                     const uint8_t* src, const float* lut, void* y, void* ws, size_t ws_bytes, void* stream);
+/* PIL's antialiased 8-bit resample of whole views at a real scale factor (Resample.c; the reference's build_image_lmdb.py:78 resizes
+ * every 480 x 640 render to 248 x 330 with ANTIALIAS = LANCZOS, timm's Resize(248) in precompute_img_features_vit.py:51-52 does it
+ * bicubically): src uint8 [n][H][W][3] -> Image.resize((OW, OH), filter) of every view, of which only the window of w x h pixels at
+ * (x0, y0) is computed and written: dst uint8 [n][h][w][3].  Bit for bit PIL's result: two passes, horizontal first, the filter
+ * support scaled by the reduction factor, 22-bit fixed-point taps, a uint8 intermediate; an axis whose size does not change is
+ * not resampled.
+ * hamt_image_resample_taps is a HOST function (no device, no stream): PIL's precompute_coeffs + normalize_coeffs_8bpc for the
+ * output coordinates [first, first + count) of an axis resized in -> out, computed in double with the host's libm.  xmin[count],
+ * xcnt[count]: first input coordinate and number of taps; k[count][ksize]: the taps, zero beyond xcnt.  Returns the number of
+ * taps per coordinate the geometry needs (`ksize` must be at least that); with all three arrays NULL it only returns that number.
+ * hamt_image_resample takes one table per axis, for the WINDOW's columns (count = w, first = x0) and rows (count = h, first = y0),
+ * each laid out as int32 xmin[count] | xcnt[count] | k[count][kx or ky], once in host memory (argument checks and LDS sizing; read
+ * during the call only) and once in device memory (read by the kernel).  The table of an axis whose size does not change is not
+ * read and may be NULL.  One launch; no scratch.  An unknown filter, an empty window or one outside (OH, OW), a table whose bounds
+ * leave the view, null pointers, or a geometry whose tables and one output row's input rows exceed the 160 KiB of LDS:
+ * HAMT_ERR_ARG, and nothing is launched. */
+enum { HAMT_RESAMPLE_BICUBIC = 0 /* a = -0.5, support 2 */, HAMT_RESAMPLE_LANCZOS = 1 /* support 3; PIL's former ANTIALIAS */ };
+typedef struct {
+  int n, H, W;                       /* views and their size */
+  int OH, OW;                        /* size of the whole resized view */
+  int x0, y0, w, h;                  /* the window of it that is written */
+  int filter;                        /* HAMT_RESAMPLE_* */
+  int kx, ky;                        /* taps per entry of the column / row table */
+} hamt_image_resample_desc;
+int hamt_image_resample_taps(int in, int out, int filter, int first, int count, int32_t* xmin, int32_t* xcnt, int32_t* k, int ksize);
+int hamt_image_resample(const hamt_image_resample_desc* d, const int32_t* xtab_host, const int32_t* ytab_host, const int32_t* xtab_dev,
+                        const int32_t* ytab_dev, const uint8_t* src, uint8_t* dst, void* stream);
 int hamt_add3(size_t n, const float* a, const float* b, const float* c, float* out, void* stream);
 int hamt_dropout(size_t n, const float* x, float* y, float p, uint32_t call_id, const uint64_t* rng, void* stream);
 int hamt_cast_f32_bf16(size_t n, const float* x, void* y, void* stream);

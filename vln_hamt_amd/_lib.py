@@ -83,6 +83,13 @@ class ImagePrepDesc(C.Structure):
     _fields_ = [("n", i32), ("n_src", i32), ("H", i32), ("W", i32), ("layout", i32), ("ldy", i32), ("dtype_y", i32), ("Rpad", i32)]
 
 
+RESAMPLE_BICUBIC, RESAMPLE_LANCZOS = 0, 1                               # HAMT_RESAMPLE_*
+
+
+class ImageResampleDesc(C.Structure):       # hamt_image_resample_desc
+    _fields_ = [(n, i32) for n in ("n", "H", "W", "OH", "OW", "x0", "y0", "w", "h", "filter", "kx", "ky")]
+
+
 # name -> argtypes (every entry point of include/hamt.h; tests/test_abi.py cross-checks against the header)
 WGRAD_TABLE_ENTRY = 112     # HAMT_WGRAD_TABLE_ENTRY
 
@@ -137,6 +144,8 @@ SIGNATURES = {
     "hamt_sum_rows": [i32, i32, i32, vp, i32, vp, vp, vp],
     "hamt_patchify": [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp],
     "hamt_image_prep": [C.POINTER(ImagePrepDesc), vp, vp, vp, vp, vp, vp, sz, vp],
+    "hamt_image_resample_taps": [i32, i32, i32, i32, i32, vp, vp, vp, i32],
+    "hamt_image_resample": [C.POINTER(ImageResampleDesc), vp, vp, vp, vp, vp, vp, vp],
     "hamt_add3": [sz, vp, vp, vp, vp, vp],
     "hamt_dropout": [sz, vp, vp, f32, u32, vp, vp],
     "hamt_cast_f32_bf16": [sz, vp, vp, vp],

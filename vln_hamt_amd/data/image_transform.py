@@ -175,6 +175,109 @@ def resize_bicubic_u8(crop: np.ndarray) -> np.ndarray:
     return _pass(_pass(crop, w, 1), h, 0)
 
 
+# ------------------------------------------------------------------------------------------------ whole-view resample
+# Image.resize((OW, OH), BICUBIC | LANCZOS) of a whole view at a real scale factor: what the reference's preprocessing runs on every
+# 480 x 640 render (build_image_lmdb.py:78 with ANTIALIAS = LANCZOS for the stored views; timm's Resize(248), bicubic, in
+# precompute_img_features_vit.py:51-52).  `hamt_image_resample` (csrc/image_resample.hip) is the GPU path, `resample_u8` the CPU path.
+RESAMPLE_FILTERS = {"bicubic": 0, "lanczos": 1}                # HAMT_RESAMPLE_*
+_SUPPORT = {"bicubic": 2.0, "lanczos": 3.0}
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x                                     # libm's sin, as PIL's: numpy's vectorised sin may differ in the last bit
+
+
+def _lanczos(x):
+    return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+
+
+def filter_taps(in_size: int, out_size: int, filter: str = "bicubic", first: int = 0, count=None):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc for output coordinates [first, first + count) of an axis resized
+    in_size -> out_size -> (xmin [count], xcnt [count], k [count, ksize] int32, zero beyond xcnt).  `resample_taps` is the
+    bicubic, 224-output case of this, kept as it is for the crop-box path."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"resample filter {filter!r}: one of {sorted(RESAMPLE_FILTERS)}")
+    count = out_size - first if count is None else count
+    scale = np.float64(in_size) / np.float64(out_size)
+    fs = max(scale, np.float64(1.0))
+    support, ss = _SUPPORT[filter] * fs, 1.0 / fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(first, first + count, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
+    cnt = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    w = np.zeros((count, ksize), np.float64)
+    ww = np.zeros(count, np.float64)
+    for x in range(ksize):                                  # sequential sum, as the C loop
+        arg = (x + xmin - center + 0.5) * ss
+        wx = _cubic(arg) if filter == "bicubic" else np.array([_lanczos(float(a)) for a in arg], np.float64).reshape(arg.shape)
+        wx = np.where(x < cnt, wx, 0.0)
+        w[:, x] = wx
+        ww = ww + wx
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    k = np.where(w < 0.0, np.trunc(-0.5 + w * 4194304.0), np.trunc(0.5 + w * 4194304.0)).astype(np.int32)
+    k[np.arange(ksize)[None, :] >= cnt[:, None]] = 0
+    return xmin.astype(np.int32), cnt.astype(np.int32), k
+
+
+def resample_pass_u8(img: np.ndarray, axis: int, taps) -> np.ndarray:
+    """one 8-bit pass of PIL's resample along `axis` of a uint8 array: clip8((2^21 + sum k p) >> 22) in int32.  The sum is taken as
+    a product with the dense (out, in) tap matrix in float64, where it is exact (|sum| < 2^33), and wrapped to int32 as C would."""
+    xmin, cnt, k = taps
+    in_size = img.shape[axis]
+    dense = np.zeros((len(xmin), in_size), np.float64)
+    for t in range(k.shape[1]):
+        rows = np.nonzero(t < cnt)[0]
+        dense[rows, xmin[rows] + t] = k[rows, t]
+    src = np.moveaxis(img, axis, -1)
+    out = np.empty(src.shape[:-1] + (len(xmin),), np.uint8)
+    flat_in, flat_out = src.reshape(-1, in_size), out.reshape(-1, len(xmin))
+    for r0 in range(0, len(flat_in), 1 << 15):                                          # (bounds the float64 copy)
+        acc = (flat_in[r0:r0 + (1 << 15)].astype(np.float64) @ dense.T).astype(np.int64).astype(np.int32)
+        flat_out[r0:r0 + (1 << 15)] = np.clip((acc + (1 << 21)) >> 22, 0, 255)
+    return np.moveaxis(out, -1, axis)
+
+
+def resample_u8(img: np.ndarray, size, filter: str = "bicubic", window=None) -> np.ndarray:
+    """uint8 (..., H, W, 3) -> the window (x0, y0, w, h) (default: all) of `Image.fromarray(view).resize((OW, OH), filter)` for
+    size = (OH, OW), uint8 (..., h, w, 3): horizontal pass first, over the input rows the window's vertical taps need; an axis
+    whose size does not change is not resampled, as in PIL."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim < 3 or img.shape[-1] != 3:
+        raise ValueError(f"resample_u8: expected uint8 (..., H, W, 3), got {img.dtype} {img.shape}")
+    H, W = img.shape[-3], img.shape[-2]
+    OH, OW = int(size[0]), int(size[1])
+    x0, y0, w, h = (0, 0, OW, OH) if window is None else (int(v) for v in window)
+    if OH < 1 or OW < 1 or w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > OW or y0 + h > OH:
+        raise ValueError(f"resample_u8: window ({x0}, {y0}, {w}, {h}) empty or outside the {OH} x {OW} result")
+    ax_y, ax_x = img.ndim - 3, img.ndim - 2
+    if OH == H:
+        img = np.take(img, np.arange(y0, y0 + h), axis=ax_y)
+    else:
+        ty = filter_taps(H, OH, filter, y0, h)
+        lo, hi = int(ty[0][0]), int(ty[0][-1] + ty[1][-1])
+        img = np.take(img, np.arange(lo, hi), axis=ax_y)                               # the rows PIL's horizontal pass covers
+        ty = (ty[0] - lo, ty[1], ty[2])
+    img = np.take(img, np.arange(x0, x0 + w), axis=ax_x) if OW == W else resample_pass_u8(img, ax_x, filter_taps(W, OW, filter, x0, w))
+    if OH != H:
+        img = resample_pass_u8(img, ax_y, ty)
+    return np.ascontiguousarray(img)
+
+
+def eval_resize_geometry(H: int, W: int):
+    """timm's eval transform at crop_pct 0.9 on an H x W view -> (OH, OW, window): Resize(248) puts the short side at 248 and the
+    long side at int(248 * long / short), CenterCrop(224) cuts at int(round((side - 224) / 2.0)) -- `draw_eval_params`' rounding.
+    window = (x0, y0, 224, 224) in the resized view."""
+    short = int(math.floor(IMGSIZE / 0.9))
+    if H <= W:
+        OH, OW = short, int(short * W / H)
+    else:
+        OH, OW = int(short * H / W), short
+    return OH, OW, (int(round((OW - IMGSIZE) / 2.0)), int(round((OH - IMGSIZE) / 2.0)), IMGSIZE, IMGSIZE)
+
+
 # ------------------------------------------------------------------------------------------------ colour jitter
 def grey(img: np.ndarray) -> np.ndarray:
     v = img.astype(np.int32)

@@ -8,9 +8,12 @@ of BASELINE config 4), the eval transform runs on the device (`hamt_image_prep`,
 (`forward_features(cls_tail=True)`).  The classifier head is one fp32 GEMM whatever the backbone's precision: n x D x C is ~0.004 %
 of the work, and the logits -- the MRC task's soft labels, `hist_img_probs` -- then carry only the features' error.
 
-Raw 480 x 640 renders are out of scope: they need a real resize in front of the crop (`draw_eval_params` raises on any view whose
-short side is not 248).  The LMDB views were resized with ANTIALIAS where the reference's own extraction let timm resize
-bicubically, so features made from the LMDB are not the reference's bit for bit.
+Raw renders (480 x 640 from the simulator) need a real resize in front of the crop, which the reference's extraction lets timm's
+`Resize(248)` do bicubically (precompute_img_features_vit.py:51-52, 96).  With `resize="bicubic"` the extractor does the same on the
+device: `hamt_image_resample`, PIL's antialiased bicubic resample windowed to the centre 224 x 224, then `hamt_image_prep` with the
+identity record, then the backbone.  The default (`resize=None`) accepts stored views only, whose short side is 248
+(`draw_eval_params` raises on anything else).  The LMDB views were resized with ANTIALIAS, so features made from the LMDB are not
+the reference's bit for bit; features made from the renders see the reference's own pixels.
 """
 from __future__ import annotations
 
@@ -27,7 +30,8 @@ from .. import _lib as L
 from .. import ops, streams
 from ..data.image_data import N_VIEWS, PanoImageStore
 from ..data.image_prep import image_prep
-from ..data.image_transform import VIEW_DTYPE, draw_eval_params
+from ..data.image_resample import image_resample
+from ..data.image_transform import IMGSIZE, RESAMPLE_FILTERS, VIEW_DTYPE, draw_eval_params, eval_resize_geometry, make_record
 from ..model.vision_transformer import VisionTransformer
 
 MODEL_CONFIGS = {"vit_base_patch16_224": dict(img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0)}
@@ -66,11 +70,11 @@ def backbone_state_dict(ckpt) -> "OrderedDict[str, torch.Tensor]":
 
 
 def build_feature_extractor(model_name="vit_base_patch16_224", checkpoint_file=None, num_classes=1000, hamt_precision="bf16",
-                            cls_tail=True, vit_kwargs: Optional[dict] = None, device="cuda") -> "ViewFeatureExtractor":
+                            cls_tail=True, vit_kwargs: Optional[dict] = None, device="cuda", resize: Optional[str] = None) -> "ViewFeatureExtractor":
     """precompute_img_features_vit.py:42-54.  `checkpoint_file`: a path for `torch.load`, or the loaded object.  None raises: the
     reference downloads timm's pretrained weights in that case and there is no download here.  `vit_kwargs` overrides the named
     model's constructor arguments (tests use a 2-block model).  Loading is strict: unknown and missing keys are named in the error.
-    A checkpoint without `head.*` gives an extractor without logits."""
+    A checkpoint without `head.*` gives an extractor without logits.  `resize`: see `ViewFeatureExtractor`."""
     if checkpoint_file is None:
         raise ValueError("build_feature_extractor: checkpoint_file is required (the reference would download timm's pretrained "
                          f"'{model_name}' here; this project never downloads)")
@@ -87,16 +91,21 @@ def build_feature_extractor(model_name="vit_base_patch16_224", checkpoint_file=N
     if unknown or missing:
         raise ValueError(f"build_feature_extractor: checkpoint does not fit '{model_name}': unknown keys {unknown}, missing keys {missing}")
     model.load_state_dict(sd, strict=True)
-    return ViewFeatureExtractor(model.to(device), cls_tail=cls_tail)
+    return ViewFeatureExtractor(model.to(device), cls_tail=cls_tail, resize=resize)
 
 
 class ViewFeatureExtractor:
     """`extractor(views_u8)`: (n, 248, 330, 3) uint8 views (tensor or ndarray, host or device) -> (fts [n, D] fp32, logits [n, C] fp32
     or None), both on the model's device.  Eval records -> `hamt_image_prep` (patch rows) -> the backbone in eval mode under
-    `torch.no_grad()` -> the head as an fp32 GEMM."""
+    `torch.no_grad()` -> the head as an fp32 GEMM.  `resize`: None (views whose short side is not 248 raise) or "bicubic", timm's
+    `Resize(248)`: such views, raw (n, 480, 640, 3) renders, are first resampled on the device (`hamt_image_resample`, only the
+    centre 224 x 224 of the resized view is computed) and then take the same path with the identity record."""
 
-    def __init__(self, model: VisionTransformer, cls_tail: bool = True):
+    def __init__(self, model: VisionTransformer, cls_tail: bool = True, resize: Optional[str] = None):
+        if resize is not None and resize not in RESAMPLE_FILTERS:
+            raise ValueError(f"ViewFeatureExtractor: resize {resize!r}: None or one of {sorted(RESAMPLE_FILTERS)}")
         self.model = model.eval()
+        self.resize = resize
         self.cls_tail = bool(cls_tail)
         self.prec = model.patch_embed.prec
         self.feat_size = model.embed_dim
@@ -116,12 +125,13 @@ class ViewFeatureExtractor:
             raise ValueError("image logits were asked for, and the checkpoint this extractor was built from has no classifier head "
                              "(`head.weight` / `head.bias`): a pretraining checkpoint carries the backbone only")
 
-    def _records(self, n, H, W, dev):
-        key = (n, H, W, str(dev))
+    def _records(self, n, H, W, dev, identity=False):
+        key = (n, H, W, str(dev), identity)
         r = self._recs.get(key)
         if r is None:
             recs = np.zeros((n,), VIEW_DTYPE)
-            recs[:] = draw_eval_params(H, W)                   # raises for views another size than the stored 248 x 330
+            # a 1:1 bicubic pass has the taps [0, 2^22, 0, 0] and copies: the centre crop of a stored view, or all of a resampled one
+            recs[:] = make_record(box=(0, 0, IMGSIZE, IMGSIZE)) if identity else draw_eval_params(H, W)    # raises for a short side other than 248
             recs["src"] = np.arange(n)
             r = self._recs[key] = (recs, torch.from_numpy(recs.view(np.uint8).copy()).to(dev))
             torch.cuda.current_stream(dev).synchronize()       # (once per batch size: any stream may use the device copy next)
@@ -136,9 +146,15 @@ class ViewFeatureExtractor:
         if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3:
             raise ValueError(f"views: expected uint8 (n, H, W, 3), got {src.dtype} {tuple(src.shape)}")
         n, H, W = src.shape[0], src.shape[1], src.shape[2]
-        recs, recs_dev = self._records(n, H, W, src.device)
+        src = src.contiguous()
+        OH, OW, window = eval_resize_geometry(H, W)
+        resampled = self.resize is not None and (OH, OW) != (H, W)
+        if resampled:                                          # Resize(248) + CenterCrop(224) in one launch
+            src = image_resample(src, (OH, OW), self.resize, window)
+            H = W = IMGSIZE
+        recs, recs_dev = self._records(n, H, W, src.device, identity=resampled)
         self.model.eval()
-        rows = image_prep(src.contiguous(), recs, recs_dev, layout="patches", dtype=torch.bfloat16 if self.prec == "bf16" else torch.float32)
+        rows = image_prep(src, recs, recs_dev, layout="patches", dtype=torch.bfloat16 if self.prec == "bf16" else torch.float32)
         fts = self.model.forward_features(rows, cls_tail=self.cls_tail)
         out = None
         if logits:
