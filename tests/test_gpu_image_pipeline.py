@@ -132,6 +132,40 @@ def test_two_runs_identical_and_scratch_content_irrelevant():
     assert float(a[4].abs().max()) == 0.0
 
 
+def test_largest_supported_box_equals_numpy_bitwise():
+    """784 = 3.5 x 224 is the largest box side the tap tables hold: 15 of their 16 columns on both axes and the largest tile of
+    horizontal-pass rows.  Every third source row is saturated to 0 / 255, so both sides of clip8 are reached."""
+    from vln_hamt_amd.data.image_prep import image_prep
+    views = np.random.default_rng(31).integers(0, 256, (2, 784, 784, 3), dtype=np.uint8)
+    views[:, 0::6], views[:, 3::6] = 0, 255
+    recs = np.array([T.make_record((0, 0, 784, 784)), T.make_record((0, 0, 784, 17), src=1), T.make_record((0, 0, 17, 784)),
+                     T.make_record((0, 0, 784, 784), True, (1, 0, 2), (1.3, 0.7, 1.2), src=1)], T.VIEW_DTYPE)
+    want = torch.from_numpy(T.transform_views(views, recs))
+    got = image_prep(torch.from_numpy(views).to(DEV), recs).cpu()
+    bad = (got != want).flatten(1).sum(1)
+    assert int(bad.sum()) == 0, [(i, int(b)) for i, b in enumerate(bad) if b]
+    assert _bits(got, want)
+
+
+def test_box_beyond_the_tap_tables_is_refused_and_launches_nothing():
+    from vln_hamt_amd.data.image_prep import norm_table_on
+    H = W = 800
+    src = torch.zeros((1, H, W, 3), dtype=torch.uint8, device=DEV)
+    lib, st = L.load(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    lut = norm_table_on(torch.device(DEV))
+    ws = torch.empty(L.workspace_bytes(L.WS_IMAGE_PREP, 2), dtype=torch.uint8, device=DEV)
+    for box in ((0, 0, 785, 100), (0, 0, 100, 785)):
+        recs = np.array([T.make_record((10, 10, 100, 100)), T.make_record(box)], T.VIEW_DTYPE)
+        rdev = torch.from_numpy(recs.view(np.uint8).copy()).to(DEV)
+        out = torch.full((2, 3, 224, 224), 7.0, device=DEV)
+        rc = lib.hamt_image_prep(C.byref(L.ImagePrepDesc(2, 1, H, W, L.IMAGE_NCHW, 0, L.HAMT_F32, 0)), C.c_void_p(recs.ctypes.data),
+                                 C.c_void_p(rdev.data_ptr()), C.c_void_p(src.data_ptr()), C.c_void_p(lut.data_ptr()), C.c_void_p(out.data_ptr()),
+                                 C.c_void_p(ws.data_ptr()), ws.numel(), st)
+        assert rc == -2 and "more than 16 taps" in L.last_error(), (rc, L.last_error())           # HAMT_ERR_UNSUPPORTED
+        torch.cuda.synchronize()
+        assert float((out - 7.0).abs().max()) == 0.0            # not even the valid slot was written
+
+
 def test_bad_arguments_launch_nothing():
     from vln_hamt_amd.data.image_prep import image_prep
     H, W = 248, 330

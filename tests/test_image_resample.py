@@ -55,15 +55,23 @@ def test_resample_u8_batches_and_refuses_bad_windows():
         resample_u8(v, (OH, OW), "nearest")
 
 
-@pytest.mark.parametrize("name,filt", R.keys(), ids=lambda v: str(v))
+CROP_SIDES = (1, 45, 223, 224, 225, 500, 784)          # box sides of the crop path, side -> 224: upsampling, 1:1, the 15-tap maximum
+
+
+@pytest.mark.parametrize("name,filt", R.keys() + [(side, "bicubic") for side in CROP_SIDES], ids=lambda v: str(v))
 def test_library_taps_equal_numpy_taps(name, filt):
     """`hamt_image_resample_taps` is a host function: PIL's coefficients integer for integer, for both axes of every case, over the
-    whole axis and over the window's coordinates"""
+    whole axis and over the window's coordinates.  The crop sides run the tap function `image_prep_resize_kernel` runs on the device:
+    one source (csrc/pil_resample.h), instantiated for the bicubic filter on both sides."""
     from vln_hamt_amd.data.image_resample import library_taps
     from vln_hamt_amd.data.image_transform import filter_taps
-    H, W, OH, OW, win, _ = R.CASES[name]
-    x0, y0, w, h = win if win else (0, 0, OW, OH)
-    for i, o, first, count in ((W, OW, 0, OW), (H, OH, 0, OH), (W, OW, x0, w), (H, OH, y0, h)):
+    if name in CROP_SIDES:
+        axes = ((name, 224, 0, 224), (name, 224, 208, 16))
+    else:
+        H, W, OH, OW, win, _ = R.CASES[name]
+        x0, y0, w, h = win if win else (0, 0, OW, OH)
+        axes = ((W, OW, 0, OW), (H, OH, 0, OH), (W, OW, x0, w), (H, OH, y0, h))
+    for i, o, first, count in axes:
         a, b = library_taps(i, o, filt, first, count), filter_taps(i, o, filt, first, count)
         for u, v in zip(a, b):
             assert u.dtype == v.dtype == np.int32 and u.shape == v.shape and np.array_equal(u, v), (name, filt, i, o)

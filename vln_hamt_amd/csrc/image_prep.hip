@@ -2,9 +2,8 @@
 // batch of uint8 views: crop -> PIL-BICUBIC resize to 224 x 224 -> flip -> colour jitter -> x / 255 -> (x - 0.5) / 0.5.
 //
 // The result is PIL's bit for bit, so the arithmetic is PIL's (Resample.c, Blend.c, Convert.c), not an approximation of it:
-//  * resize: two passes of 8-bit resampling over the CROPPED view.  Tap weights in double in PIL's order of operations (no FMA
-//    contraction in this file), normalised, converted to 22-bit fixed point; a pass is clip8((2^21 + sum k p) >> 22) in int32;
-//    the horizontal pass's uint8 result feeds the vertical pass.
+//  * resize: two passes of 8-bit resampling over the CROPPED view, bicubic.  The tap function and the arithmetic of a pass are
+//    pil_resample.h's, shared with image_resample.hip; the taps are made here on the device, per view slot.
 //  * jitter: Image.blend(degenerate, image, factor) in float32, truncated (clipped when the factor is outside [0, 1]), rounded
 //    to uint8 after every op.  The contrast op needs the mean grey value of the whole image as it is when the op runs: the
 //    first kernel stops in front of it and leaves one integer partial sum per row tile, the second kernel adds the 14 partials
@@ -16,8 +15,7 @@
 // kernel 2 (grid stride over 4-pixel groups): contrast and the ops after it -> table -> NCHW fp32, or the rows hamt_patchify
 //   would make of that tensor (fp32 / bf16).
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "pil_resample.h"
 
 #define IP_OUT 224
 #define IP_TR 16                         // output rows per tile
@@ -32,46 +30,8 @@
 
 size_t hamt_image_prep_ws_bytes(int n) { return (size_t)(n > 0 ? n : 0) * IP_SLOT; }
 
-__host__ __device__ static inline int ip_ksize(int in) {
-  const double fs = (double)in / IP_OUT > 1.0 ? (double)in / IP_OUT : 1.0;
-  return (int)ceil(2.0 * fs) * 2 + 1;
-}
+static inline int ip_ksize(int in) { return pil_ksize(in, IP_OUT, pil_bicubic::support); }
 
-// PIL's bicubic_filter (a = -0.5)
-__device__ __forceinline__ double ip_cubic(double x) {
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((1.5 * x - 2.5) * x) * x + 1.0;
-  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;
-  return 0.0;
-}
-
-// PIL's precompute_coeffs + normalize_coeffs_8bpc for output coordinate xx of a side of `in` pixels (box origin 0)
-__device__ void ip_make_taps(int xx, int in, int* __restrict__ k, int cap, int* xmin, int* xcnt) {
-  const double scale = (double)in / IP_OUT;
-  const double fs = scale < 1.0 ? 1.0 : scale;
-  const double support = 2.0 * fs, ss = 1.0 / fs;
-  const double center = (xx + 0.5) * scale;
-  int x0 = (int)(center - support + 0.5);
-  if (x0 < 0) x0 = 0;
-  int x1 = (int)(center + support + 0.5);
-  if (x1 > in) x1 = in;
-  int cnt = x1 - x0;
-  if (cnt > cap) cnt = cap;
-  double ww = 0.0;
-  for (int x = 0; x < cnt; ++x) ww += ip_cubic((x + x0 - center + 0.5) * ss);
-  for (int x = 0; x < cnt; ++x) {
-    double w = ip_cubic((x + x0 - center + 0.5) * ss);
-    if (ww != 0.0) w /= ww;
-    k[x] = w < 0.0 ? (int)(-0.5 + w * 4194304.0) : (int)(0.5 + w * 4194304.0);
-  }
-  *xmin = x0;
-  *xcnt = cnt;
-}
-
-__device__ __forceinline__ int ip_clip8(int acc) {
-  const int v = acc >> 22;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
 __device__ __forceinline__ int ip_grey(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 // Image.blend(degenerate d, image p, factor f)
 __device__ __forceinline__ int ip_blend(int d, int p, float f) {
@@ -110,8 +70,8 @@ __global__ __launch_bounds__(256) void image_prep_resize_kernel(const hamt_image
   int* ycnt = ymin + IP_TR;
   int* red = ycnt + IP_TR;
   uint8_t* tmp = (uint8_t*)(red + 4);
-  if (tid < IP_OUT) ip_make_taps(tid, v.width, xk + tid * KX, KX, xmin + tid, xcnt + tid);
-  else if (tid < IP_OUT + IP_TR) ip_make_taps(tile * IP_TR + tid - IP_OUT, v.height, yk + (tid - IP_OUT) * IP_KMAX, IP_KMAX, ymin + tid - IP_OUT, ycnt + tid - IP_OUT);
+  if (tid < IP_OUT) pil_taps<pil_bicubic>(tid, v.width, IP_OUT, xk + tid * KX, KX, xmin + tid, xcnt + tid);
+  else if (tid < IP_OUT + IP_TR) pil_taps<pil_bicubic>(tile * IP_TR + tid - IP_OUT, v.height, IP_OUT, yk + (tid - IP_OUT) * IP_KMAX, IP_KMAX, ymin + tid - IP_OUT, ycnt + tid - IP_OUT);
   __syncthreads();
   const int r_lo = ymin[0];
   int rows = ymin[IP_TR - 1] + ycnt[IP_TR - 1] - r_lo;
@@ -120,12 +80,7 @@ __global__ __launch_bounds__(256) void image_prep_resize_kernel(const hamt_image
   const uint8_t* img = src + (size_t)v.src * H * W * 3 + ((size_t)(v.top + r_lo) * W + v.left) * 3;
   for (int i = tid; i < rows * IP_ROWB; i += 256) {
     const int r = i / IP_ROWB, rem = i % IP_ROWB, x = rem / 3, c = rem % 3;
-    const int* k = xk + x * KX;
-    const int n = xcnt[x];
-    const uint8_t* p = img + (size_t)r * W * 3 + xmin[x] * 3 + c;
-    int acc = 1 << 21;
-    for (int t = 0; t < n; ++t) acc += (int)p[t * 3] * k[t];
-    tmp[i] = (uint8_t)ip_clip8(acc);
+    tmp[i] = (uint8_t)pil_sample1(img + (size_t)r * W * 3 + xmin[x] * 3 + c, 3, xk + x * KX, xcnt[x]);
   }
   __syncthreads();
   // ---- vertical pass, flip, the ops in front of contrast, grey sum
@@ -134,16 +89,11 @@ __global__ __launch_bounds__(256) void image_prep_resize_kernel(const hamt_image
   int gsum = 0;
   for (int i = tid; i < IP_TR * IP_OUT; i += 256) {
     const int yy = i / IP_OUT, x = i % IP_OUT;
-    const int* k = yk + yy * IP_KMAX;
     const int y0 = ymin[yy] - r_lo;
     int n = ycnt[yy];
     if (y0 + n > rows) n = rows - y0;
-    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-    for (int t = 0; t < n; ++t) {
-      const uint8_t* p = tmp + ((y0 + t) * IP_OUT + x) * 3;
-      a0 += (int)p[0] * k[t]; a1 += (int)p[1] * k[t]; a2 += (int)p[2] * k[t];
-    }
-    int r = ip_clip8(a0), g = ip_clip8(a1), b = ip_clip8(a2);
+    int r, g, b;
+    pil_sample3(tmp + (y0 * IP_OUT + x) * 3, IP_ROWB, yk + yy * IP_KMAX, n, r, g, b);
     for (int j = 0; j < cpos && j < 3; ++j) ip_apply((v.order >> (2 * j)) & 3, v, 0, r, g, b);
     if (cpos < 3) gsum += ip_grey(r, g, b);
     const int xo = v.flip ? IP_OUT - 1 - x : x;

@@ -4,47 +4,24 @@
 // CenterCrop(224)).  hamt_image_prep (image_prep.hip) resizes a crop BOX to 224 x 224; this file resizes the whole view to
 // (OH, OW) and writes only a window of the result, so that "resize, then cut the centre" never computes what the cut drops.
 //
-// The result is PIL's bit for bit:
-//  * taps: hamt_image_resample_taps, on the HOST, in double, in PIL's order of operations (precompute_coeffs: sequential sum,
-//    normalise; normalize_coeffs_8bpc: 22-bit fixed point with the +-0.5 rule).  Lanczos needs sin(): the host's libm is what PIL
-//    calls, the device's sin is not, so no tap is ever computed on the device.  No FMA contraction in this file.
-//  * passes: horizontal first, clip8((2^21 + sum k p) >> 22) in int32, the uint8 result feeds the vertical pass.
+// The result is PIL's bit for bit.  The tap function and the arithmetic of a pass are pil_resample.h's, shared with image_prep.hip:
+//  * taps: hamt_image_resample_taps, on the HOST.  Lanczos needs sin(): the host's libm is what PIL calls, the device's sin is not,
+//    so no tap is ever computed on the device; the kernel loads the caller's host-made tables.
+//  * passes: horizontal first, the uint8 result feeds the vertical pass.
 //  * an axis whose input and output sizes are equal is not resampled (PIL skips that pass): the kernel gives it the table
-//    (xmin = coordinate, one tap of 2^22), with which the pass arithmetic returns the byte it reads.
+//    (xmin = coordinate, one tap of 1.0 = PIL_ONE), with which the pass arithmetic returns the byte it reads.
 //
 // kernel (one workgroup per view and tile of TR output rows): both tables -> LDS; horizontal pass of exactly the input rows the
 // tile's vertical taps cover, window columns only, into LDS as uint8; vertical pass out of LDS -> the window.  No scratch, no atomics.
 #include "common.h"
-
-#include <cmath>
-#include <vector>
-
-#pragma clang fp contract(off)
+#include "pil_resample.h"
 
 #define IR_TR 16                         // output rows per tile, halved by the launcher until the request fits
 #define IR_LDS_MAX (160 * 1024)          // LDS of one CU
-#define IR_ONE (1 << 22)                 // 1.0 in the 22-bit fixed point of the taps
 
 // ------------------------------------------------------------------------------------------------ taps (host)
-static double ir_cubic(double x) {       // PIL's bicubic_filter (a = -0.5)
-  if (x < 0.0) x = -x;
-  if (x < 1.0) return ((1.5 * x - 2.5) * x) * x + 1.0;
-  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;
-  return 0.0;
-}
-static double ir_sinc(double x) {
-  if (x == 0.0) return 1.0;
-  x = x * 3.14159265358979323846;
-  return sin(x) / x;
-}
-static double ir_lanczos(double x) {     // PIL's lanczos_filter: truncated sinc
-  if (-3.0 <= x && x < 3.0) return ir_sinc(x) * ir_sinc(x / 3);
-  return 0.0;
-}
-
 static int ir_ksize(int in, int out, int filter) {
-  const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale;
-  return (int)ceil((filter == HAMT_RESAMPLE_LANCZOS ? 3.0 : 2.0) * fs) * 2 + 1;
+  return pil_ksize(in, out, filter == HAMT_RESAMPLE_LANCZOS ? pil_lanczos::support : pil_bicubic::support);
 }
 
 extern "C" int hamt_image_resample_taps(int in, int out, int filter, int first, int count, int32_t* xmin, int32_t* xcnt, int32_t* k, int ksize) {
@@ -56,42 +33,16 @@ extern "C" int hamt_image_resample_taps(int in, int out, int filter, int first, 
   HAMT_CHECK_ARG(xmin && xcnt && k, "hamt_image_resample_taps: null pointer");
   HAMT_CHECK_ARG(first >= 0 && count >= 0 && (long long)first + count <= out, "hamt_image_resample_taps: coordinates [%d, %d + %d) of %d", first, first, count, out);
   HAMT_CHECK_ARG(ksize >= need, "hamt_image_resample_taps: ksize %d < %d", ksize, need);
-  const double scale = (double)in / out, fs = scale < 1.0 ? 1.0 : scale;
-  const double support = (filter == HAMT_RESAMPLE_LANCZOS ? 3.0 : 2.0) * fs, ss = 1.0 / fs;
-  std::vector<double> w((size_t)need);
   for (int i = 0; i < count; ++i) {
-    const int xx = first + i;
-    const double center = (xx + 0.5) * scale;
-    int x0 = (int)(center - support + 0.5);
-    if (x0 < 0) x0 = 0;
-    int x1 = (int)(center + support + 0.5);
-    if (x1 > in) x1 = in;
-    const int cnt = x1 - x0;
-    double ww = 0.0;
-    for (int x = 0; x < cnt; ++x) {
-      const double a = (x + x0 - center + 0.5) * ss;
-      w[x] = filter == HAMT_RESAMPLE_LANCZOS ? ir_lanczos(a) : ir_cubic(a);
-      ww += w[x];
-    }
     int32_t* kk = k + (size_t)i * ksize;
-    for (int x = 0; x < ksize; ++x) {
-      if (x >= cnt) { kk[x] = 0; continue; }
-      double v = w[x];
-      if (ww != 0.0) v /= ww;
-      kk[x] = v < 0.0 ? (int)(-0.5 + v * 4194304.0) : (int)(0.5 + v * 4194304.0);
-    }
-    xmin[i] = x0;
-    xcnt[i] = cnt;
+    if (filter == HAMT_RESAMPLE_LANCZOS) pil_taps<pil_lanczos>(first + i, in, out, kk, ksize, xmin + i, xcnt + i);
+    else pil_taps<pil_bicubic>(first + i, in, out, kk, ksize, xmin + i, xcnt + i);
+    for (int x = xcnt[i]; x < ksize; ++x) kk[x] = 0;
   }
   return need;
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
-__device__ __forceinline__ int ir_clip8(int acc) {
-  const int v = acc >> 22;
-  return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
 // table of one axis as the caller lays it out: xmin[cnt_out] | xcnt[cnt_out] | k[cnt_out][K]; a null table (K == 0) is the skipped
 // axis.  Copies entries [first, first + m) into LDS with the bounds clamped to the input side, so that no table content can make
 // a pass read outside its view.
@@ -113,7 +64,7 @@ __device__ __forceinline__ void ir_load_table(const int32_t* __restrict__ tab, i
     smin[i] = lo;
     scnt[i] = c;
   }
-  for (int i = tid; i < m * KS; i += 256) sk[i] = K > 0 ? tab[2 * (size_t)cnt_out + (size_t)first * K + i] : IR_ONE;
+  for (int i = tid; i < m * KS; i += 256) sk[i] = K > 0 ? tab[2 * (size_t)cnt_out + (size_t)first * K + i] : PIL_ONE;
 }
 
 __global__ __launch_bounds__(256) void image_resample_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const int32_t* __restrict__ xtab,
@@ -141,35 +92,24 @@ __global__ __launch_bounds__(256) void image_resample_kernel(const uint8_t* __re
   const uint8_t* img = src + ((size_t)view * H + r_lo) * W * 3;
   for (int i = tid; i < rows * w; i += 256) {
     const int r = i / w, x = i % w;
-    const int* k = xk + x * KXS;
-    const int n = xcnt[x];
-    const uint8_t* p = img + ((size_t)r * W + xmin[x]) * 3;
-    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-    for (int t = 0; t < n; ++t) {
-      const int kt = k[t];
-      a0 += (int)p[t * 3] * kt; a1 += (int)p[t * 3 + 1] * kt; a2 += (int)p[t * 3 + 2] * kt;
-    }
+    int c0, c1, c2;
+    pil_sample3(img + ((size_t)r * W + xmin[x]) * 3, 3, xk + x * KXS, xcnt[x], c0, c1, c2);
     uint8_t* q = tmp + (size_t)i * 3;
-    q[0] = (uint8_t)ir_clip8(a0); q[1] = (uint8_t)ir_clip8(a1); q[2] = (uint8_t)ir_clip8(a2);
+    q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
   }
   __syncthreads();
   // ---- vertical pass
   uint8_t* out = dst + ((size_t)view * h + row0) * w * 3;
   for (int i = tid; i < tr * w; i += 256) {
     const int yy = i / w, x = i % w;
-    const int* k = yk + yy * KYS;
     int yl = ymin[yy] - r_lo;
     int n = ycnt[yy];
     if (yl < 0) yl = 0;                            // (tables with decreasing bounds: PIL's never are)
     if (yl + n > rows) n = rows - yl;
-    int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-    for (int t = 0; t < n; ++t) {
-      const uint8_t* p = tmp + ((size_t)(yl + t) * w + x) * 3;
-      const int kt = k[t];
-      a0 += (int)p[0] * kt; a1 += (int)p[1] * kt; a2 += (int)p[2] * kt;
-    }
+    int c0, c1, c2;
+    pil_sample3(tmp + ((size_t)yl * w + x) * 3, w * 3, yk + yy * KYS, n, c0, c1, c2);
     uint8_t* q = out + (size_t)i * 3;
-    q[0] = (uint8_t)ir_clip8(a0); q[1] = (uint8_t)ir_clip8(a1); q[2] = (uint8_t)ir_clip8(a2);
+    q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
   }
 }
 

@@ -24,6 +24,7 @@ that cannot be replayed without them, so only the distributions (supports, proba
 """
 from __future__ import annotations
 
+import functools
 import math
 import random
 from typing import Sequence
@@ -118,69 +119,19 @@ def draw_train_params(rng, H=HEIGHT, W=WIDTH, jitter=0.4, hflip=0.5):
     return make_record(box=box, flip=flip, order=order, factors=factors)
 
 
-# ------------------------------------------------------------------------------------------------ resize
+# ------------------------------------------------------------------------------------------------ resample
+# PIL's 8-bit two-pass resample (Resample.c), once: `filter_taps` + `resample_pass_u8`.  Two callers:
+# * `resize_bicubic_u8`: a crop box -> 224 x 224, bicubic (`hamt_image_prep`, csrc/image_prep.hip, is the GPU path);
+# * `resample_u8`: Image.resize((OW, OH), BICUBIC | LANCZOS) of a whole view at a real scale factor, what the reference's preprocessing
+#   runs on every 480 x 640 render (build_image_lmdb.py:78 with ANTIALIAS = LANCZOS for the stored views; timm's Resize(248), bicubic,
+#   in precompute_img_features_vit.py:51-52); `hamt_image_resample` (csrc/image_resample.hip) is the GPU path.
+RESAMPLE_FILTERS = {"bicubic": 0, "lanczos": 1}                # HAMT_RESAMPLE_*
+_SUPPORT = {"bicubic": 2.0, "lanczos": 3.0}
+
+
 def _cubic(x):
     x = np.abs(x)
     return np.where(x < 1.0, ((1.5 * x - 2.5) * x) * x + 1.0, np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5, 0.0))
-
-
-_TAPS: dict = {}
-
-
-def resample_taps(in_size: int, out_size: int = IMGSIZE):
-    """PIL's precompute_coeffs + normalize_coeffs_8bpc (BICUBIC) -> (xmin [out], count [out], k [out, ksize] int32, zero beyond count)"""
-    key = (in_size, out_size)
-    if key in _TAPS:
-        return _TAPS[key]
-    scale = np.float64(in_size) / np.float64(out_size)
-    fs = max(scale, np.float64(1.0))
-    support, ss = 2.0 * fs, 1.0 / fs
-    ksize = int(math.ceil(support)) * 2 + 1
-    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
-    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
-    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size)
-    cnt = xmax - xmin
-    w = np.zeros((out_size, ksize), np.float64)
-    ww = np.zeros(out_size, np.float64)
-    for x in range(ksize):                                  # sequential sum, as the C loop
-        wx = np.where(x < cnt, _cubic((x + xmin - center + 0.5) * ss), 0.0)
-        w[:, x] = wx
-        ww = ww + wx
-    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
-    k = np.where(w < 0.0, np.trunc(-0.5 + w * 4194304.0), np.trunc(0.5 + w * 4194304.0)).astype(np.int32)
-    k[np.arange(ksize)[None, :] >= cnt[:, None]] = 0
-    if len(_TAPS) > 4096:
-        _TAPS.clear()
-    _TAPS[key] = (xmin, cnt, k)
-    return _TAPS[key]
-
-
-def _pass(img, in_size, axis):
-    """one 8-bit resampling pass along `axis` (0: rows, 1: columns) of a uint8 (h, w, 3) image"""
-    xmin, cnt, k = resample_taps(in_size)
-    idx = np.minimum(xmin[:, None] + np.arange(k.shape[1])[None, :], in_size - 1)        # taps beyond `count` have weight 0
-    acc = np.full((IMGSIZE, img.shape[1], 3) if axis == 0 else (img.shape[0], IMGSIZE, 3), 1 << 21, np.int32)
-    src = img.astype(np.int32)
-    for t in range(k.shape[1]):
-        if axis == 0:
-            acc += src[idx[:, t]] * k[:, t][:, None, None]
-        else:
-            acc += src[:, idx[:, t]] * k[:, t][None, :, None]
-    return np.clip(acc >> 22, 0, 255).astype(np.uint8)
-
-
-def resize_bicubic_u8(crop: np.ndarray) -> np.ndarray:
-    """uint8 (h, w, 3) -> uint8 (224, 224, 3) == Image.fromarray(crop).resize((224, 224), Image.BICUBIC)"""
-    h, w = crop.shape[:2]
-    return _pass(_pass(crop, w, 1), h, 0)
-
-
-# ------------------------------------------------------------------------------------------------ whole-view resample
-# Image.resize((OW, OH), BICUBIC | LANCZOS) of a whole view at a real scale factor: what the reference's preprocessing runs on every
-# 480 x 640 render (build_image_lmdb.py:78 with ANTIALIAS = LANCZOS for the stored views; timm's Resize(248), bicubic, in
-# precompute_img_features_vit.py:51-52).  `hamt_image_resample` (csrc/image_resample.hip) is the GPU path, `resample_u8` the CPU path.
-RESAMPLE_FILTERS = {"bicubic": 0, "lanczos": 1}                # HAMT_RESAMPLE_*
-_SUPPORT = {"bicubic": 2.0, "lanczos": 3.0}
 
 
 def _sinc(x):
@@ -196,8 +147,7 @@ def _lanczos(x):
 
 def filter_taps(in_size: int, out_size: int, filter: str = "bicubic", first: int = 0, count=None):
     """PIL's precompute_coeffs + normalize_coeffs_8bpc for output coordinates [first, first + count) of an axis resized
-    in_size -> out_size -> (xmin [count], xcnt [count], k [count, ksize] int32, zero beyond xcnt).  `resample_taps` is the
-    bicubic, 224-output case of this, kept as it is for the crop-box path."""
+    in_size -> out_size -> (xmin [count], xcnt [count], k [count, ksize] int32, zero beyond xcnt)"""
     if filter not in RESAMPLE_FILTERS:
         raise ValueError(f"resample filter {filter!r}: one of {sorted(RESAMPLE_FILTERS)}")
     count = out_size - first if count is None else count
@@ -223,21 +173,35 @@ def filter_taps(in_size: int, out_size: int, filter: str = "bicubic", first: int
 
 
 def resample_pass_u8(img: np.ndarray, axis: int, taps) -> np.ndarray:
-    """one 8-bit pass of PIL's resample along `axis` of a uint8 array: clip8((2^21 + sum k p) >> 22) in int32.  The sum is taken as
-    a product with the dense (out, in) tap matrix in float64, where it is exact (|sum| < 2^33), and wrapped to int32 as C would."""
+    """one 8-bit pass of PIL's resample along `axis` of a uint8 array: clip8((2^21 + sum k p) >> 22) in int32, wrapping as C's does.
+    Tap by tap -- one gather of every output coordinate's t-th input per tap -- over blocks that stay in the cache, each turned so
+    that the resampled axis comes first and a gather moves whole rows."""
     xmin, cnt, k = taps
-    in_size = img.shape[axis]
-    dense = np.zeros((len(xmin), in_size), np.float64)
-    for t in range(k.shape[1]):
-        rows = np.nonzero(t < cnt)[0]
-        dense[rows, xmin[rows] + t] = k[rows, t]
-    src = np.moveaxis(img, axis, -1)
-    out = np.empty(src.shape[:-1] + (len(xmin),), np.uint8)
-    flat_in, flat_out = src.reshape(-1, in_size), out.reshape(-1, len(xmin))
-    for r0 in range(0, len(flat_in), 1 << 15):                                          # (bounds the float64 copy)
-        acc = (flat_in[r0:r0 + (1 << 15)].astype(np.float64) @ dense.T).astype(np.int64).astype(np.int32)
-        flat_out[r0:r0 + (1 << 15)] = np.clip((acc + (1 << 21)) >> 22, 0, 255)
-    return np.moveaxis(out, -1, axis)
+    shape, n_out, axis = img.shape, len(xmin), axis % img.ndim
+    src = np.ascontiguousarray(img).reshape(-1, shape[axis], int(np.prod(shape[axis + 1:])))          # (lead, in, trail)
+    out = np.empty((src.shape[0], n_out, src.shape[2]), np.uint8)
+    idx = np.minimum(xmin[:, None] + np.arange(k.shape[1]), shape[axis] - 1)
+    kk = np.where(np.arange(k.shape[1]) < cnt[:, None], k, 0).astype(np.int32)          # taps beyond xcnt weigh nothing
+    step = max(1, 4096 // max(src.shape[2], 1))
+    for l in range(0, src.shape[0], step):
+        s = np.ascontiguousarray(src[l:l + step].transpose(1, 0, 2))
+        acc = np.full((n_out,) + s.shape[1:], 1 << 21, np.int32)
+        for t in range(k.shape[1]):
+            acc += s[idx[:, t]] * kk[:, t, None, None]
+        out[l:l + step] = np.clip(acc >> 22, 0, 255).transpose(1, 0, 2)
+    return out.reshape(shape[:axis] + (n_out,) + shape[axis + 1:])
+
+
+@functools.lru_cache(maxsize=4096)
+def _crop_taps(in_size: int):
+    """the crop path draws a new box size for almost every view: the taps of a side are made once"""
+    return filter_taps(in_size, IMGSIZE)
+
+
+def resize_bicubic_u8(crop: np.ndarray) -> np.ndarray:
+    """uint8 (h, w, 3) -> uint8 (224, 224, 3) == Image.fromarray(crop).resize((224, 224), Image.BICUBIC)"""
+    h, w = crop.shape[:2]
+    return resample_pass_u8(resample_pass_u8(crop, 1, _crop_taps(w)), 0, _crop_taps(h))
 
 
 def resample_u8(img: np.ndarray, size, filter: str = "bicubic", window=None) -> np.ndarray:
