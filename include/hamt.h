@@ -121,6 +121,9 @@ int hamt_gemm(const hamt_gemm_desc* d, const void* A, const void* B, void* C, co
 int hamt_gemm_ksplit(const hamt_gemm_desc* d);
 int hamt_gemm_ws(const hamt_gemm_desc* d, const void* A, const void* B, void* C, const float* bias,
                  void* aux, void* ws, size_t ws_bytes, void* stream);
+/* K slices (>= 1) that hamt_gemm_ws would use for `d` with ws_bytes of workspace, and in `name` (n bytes) the kernel it would
+ * launch, as hamt_last_kernel reports it; launches nothing, touches no device state.  Negative: bad argument. */
+int hamt_gemm_plan(const hamt_gemm_desc* d, size_t ws_bytes, char* name, size_t n);
 
 /* operand preparation for the bf16 fast path (both GEMM operands bf16, K-contiguous, K % 64 == 0):
  *   cast_pad_bf16:   y[Rpad][Cpad] (bf16) = x[R][C] (fp32), rows >= R and columns >= C zero filled

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _gemm_cases import BENCH_GEMMS, KG_GEMMS
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -137,13 +139,7 @@ def test_gemm_epilogues(prec):
     close(o16.float(), lin, 1e-2, "bf16 C")
 
 
-@pytest.mark.parametrize("layout,shape,variant", [
-    ("nt", (1280, 768, 3072), "gemm_kg_kernel<32, 2, 4"), ("nn", (1280, 768, 2304), "gemm_kg_kernel<32, 2, 4"),
-    ("nt", (1968, 768, 3072), "gemm_kg_kernel<64, 3, 2"), ("nn", (1968, 768, 2304), "gemm_kg_kernel<64, 3, 2"),
-    ("nt", (688, 768, 768), "gemm_kg_kernel<32, 2, 4"), ("nt", (100, 130, 1536), "gemm_kg_kernel<32, 2, 4"),
-    ("nn", (1301, 700, 1600), "gemm_kg_kernel<32, 2, 4"), ("nn", (2500, 520, 1664), "gemm_kg_kernel<64, 3, 2"),
-    ("nt", (5120, 768, 3072), "gemm_kg_kernel<128, 2, 2"), ("nn", (2752, 768, 2304), "gemm_kg_kernel<128, 2, 2"),
-    ("nn", (4001, 1000, 2368), "gemm_kg_kernel<128, 2, 2")])
+@pytest.mark.parametrize("layout,shape,variant", KG_GEMMS)
 def test_gemm_k_groups(layout, shape, variant):
     """Small grids with a long reduction run as K groups inside one workgroup (gemm_kg_kernel): every k-tile residue class,
     ragged edges, the run-time epilogue (bias, accumulate, bf16 output with an aux multiply, dropout + residual)."""
@@ -186,54 +182,6 @@ def test_gemm_k_groups(layout, shape, variant):
         ops.gemm(Az.to(DEV).to(torch.bfloat16), b_st[:K - 5].contiguous().to(DEV).to(torch.bfloat16), out, b_kmajor=True, prec="bf16", k_red=K)
         assert L.last_kernel().startswith("gemm_q4_kernel" if variant.startswith("gemm_kg_kernel<128") else variant), L.last_kernel()
         close(out, bf16_round(Az).double() @ bf16_round(B).double(), tol, "kg nn ragged K")
-
-
-# The step's own GEMM shapes at the benchmarked per-GPU batch (B = 64: text 5120 rows, panorama 11520, text + vision 7872 ...),
-# each on the kernel the launcher picks for it there, against fp64 products of the same bf16-rounded operands.  The smaller
-# SHAPES above never reach the 256-square two-phase tile (gemm_p8_kernel needs >= ~200 tiles and K >= 128) nor the 128-row plain
-# tile; round 2 shipped a NaN in exactly that family which only a training soak saw.
-BENCH_GEMMS = [   # (layout, M, N, K, epilogue, C dtype, kernel the launcher must pick)
-    ("nt", 5120, 2304, 768, "bias", "bf16", "gemm_p8_kernel<1, false, false, 3>"),       # text QKV: 240 tiles of 256 x 192 = one full round
-    ("nt", 7872, 2304, 768, "bias", "bf16", "gemm_fast_kernel<128, 1, false, false>"),   # packed QKV over text + vision rows: two rounds of either 256-row tile -> plain 128-row tiles
-    ("nt", 11520, 2304, 768, "bias", "bf16", "gemm_p8_kernel<1, false, false, 4>"),         # panorama QKV
-    ("nt", 5120, 3072, 768, "gelugrad", "bf16", "gemm_p8_kernel<129, false, false, 4>"),    # text FFN-1 (+ saved gelu')
-    ("nt", 11520, 3072, 768, "gelugrad", "bf16", "gemm_p8_kernel<129, false, false, 4>"),   # panorama FFN-1
-    ("nt", 5003, 2304, 768, "bias", "bf16", "gemm_p8_kernel<1, false, false, 3>"),       # ragged last tile row
-    ("nt", 5120, 2304, 768, "gelugrad", "bf16", "gemm_p8_kernel<129, false, false, 3>"), # (FFN-1's epilogue on the narrow tile)
-    ("nt", 5120, 2250, 768, "bias", "f32", "gemm_p8_kernel<1, false, false, 3>"),        # ragged last 192-column tile (138 columns), fp32 C
-    ("nt", 5120, 2318, 768, "bias", "f32", "gemm_p8_kernel<1, false, false, 4>"),           # ragged last tile column, fp32 C
-    ("nt", 11520, 768, 3072, "bias", "bf16", "gemm_p8_kernel<1, false, false, 3>"),      # panorama FFN-2
-    ("nt", 11520, 768, 3072, "drop_res", "f32", "gemm_p8_kernel<1537, false, false, 4>"),   # bias + dropout + residual (pre-LN ViT form)
-    ("nn", 5120, 3072, 768, "mulaux", "bf16", "gemm_p8_kernel<256, false, true, 4>"),       # dgrad of FFN-2 x gelu'
-    ("nn", 11520, 3072, 768, "mulaux", "bf16", "gemm_p8_kernel<256, false, true, 3>"),
-    ("nn", 11520, 768, 3072, "acc", "f32", "gemm_p8_kernel<8, false, true, 3>"),         # dgrad of FFN-1 into the residual gradient
-    ("nn", 11520, 768, 2304, "acc", "f32", "gemm_p8_kernel<8, false, true, 3>"),         # dgrad of QKV into the residual gradient
-    ("nn", 5120, 2304, 768, "none", "bf16", "gemm_p8_kernel<0, false, true, 3>"),
-    ("nn", 5013, 2248, 768, "mulaux", "bf16", "gemm_p8_kernel<256, false, true, 3>"),    # ragged rows and a ragged 192-column tile, K-strided B
-    ("nn", 5009, 3072, 768, "mulaux", "bf16", "gemm_p8_kernel<256, false, true, 4>"),       # ragged rows
-    ("nt", 5120, 768, 768, "bias", "bf16", "gemm_q4_kernel<1, false>"),                  # attention output projection: 240 tiles of 128 x 128, four-deep ring
-    ("nn", 5120, 768, 768, "none", "bf16", "gemm_q4_kernel<0, true>"),                   # its dgrad
-    ("nt", 2752, 768, 768, "bias", "f32", "gemm_q4_kernel<1, false>"),                   # vision stream (132 tiles)
-    ("nt", 1280, 768, 768, "bias", "bf16", "gemm_kg_kernel<32, 2, 4, false>"),           # (B = 16: too few 128-square tiles -- K groups on 32-row tiles)
-    ("nn", 1280, 768, 768, "none", "bf16", "gemm_kg_kernel<32, 2, 4, true>"),
-    ("nt", 5120, 1536, 768, "bias", "bf16", "gemm_fast_kernel<128, 1, false, false>"),   # key / value projection of the cross attention (N = 1536: not the q4 tile's)
-    ("nt", 5003, 760, 832, "bias", "f32", "gemm_q4_kernel<1, false>"),                   # ragged rows and columns
-    ("nn", 5003, 760, 832, "acc", "f32", "gemm_q4_kernel<8, true>"),
-    ("nn", 5120, 768, 2304, "acc", "f32", "gemm_q4_kernel<8, true>"),                    # dgrad of QKV into the residual gradient
-    ("nt", 3200, 768, 192, "bias", "bf16", "gemm_q4_kernel<1, false>"),                  # the shortest reduction the ring takes (3 k-tiles)
-    ("nt", 3200, 768, 256, "none", "bf16", "gemm_q4_kernel<0, false>"),
-    ("nt", 4096, 4096, 64, "bias", "bf16", "gemm_fast_kernel<128, 1, false, false>"),    # 128-row plain tile
-    ("nn", 4096, 4096, 64, "acc", "f32", "gemm_fast_kernel<128, 8, false, true>"),
-    ("nt", 5120, 3072, 768, "gelugrad8", "bf16", "gemm_p8_kernel<129, false, false, 4>"),   # text FFN-1, gelu' saved as one byte (HAMT_U8G)
-    ("nt", 2752, 3072, 768, "gelugrad8", "bf16", None),                                      # vision stream
-    ("nt", 389, 3068, 768, "gelugrad8", "bf16", None),                                       # ragged rows / columns: byte-wise tail of the code image
-    ("nn", 5120, 3072, 768, "mulaux8", "bf16", "gemm_p8_kernel<256, false, true, 4>"),       # dgrad of FFN-2 x the one-byte gelu'
-    ("nn", 11520, 3072, 768, "mulaux8", "bf16", "gemm_p8_kernel<256, false, true, 3>"),
-    ("nn", 2752, 3072, 768, "mulaux8", "bf16", None),
-    ("nn", 389, 3068, 768, "mulaux8", "bf16", None),
-    ("nt", 5120, 768, 3072, "bias", "bf16", "gemm_q4_kernel<1, false>"),                  # text FFN-2
-    ("nn", 5120, 768, 3072, "acc", "f32", "gemm_q4_kernel<8, true>"),
-]
 
 
 @pytest.mark.parametrize("layout,M,N,K,epi,cdt,kernel", BENCH_GEMMS, ids=[f"{s[0]}-{s[1]}x{s[2]}x{s[3]}-{s[4]}-{s[5]}" for s in BENCH_GEMMS])

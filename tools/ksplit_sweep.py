@@ -46,7 +46,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--ks", default="0,1,2,3,4,6,8")
     ap.add_argument("--bm", default="0,64,128")
-    ap.add_argument("--kg", default="", help="comma list of HAMT_KG variants (10 * tile rows + groups), e.g. 322,323,642,643: sweeps these instead")
+    ap.add_argument("--kg", default="", help="comma list of HAMT_KG variants (100 * tile rows + 10 * groups + ring depth), e.g. 3223,3232,3224,6423,6432,12822: sweeps these instead")
     ap.add_argument("--worker", action="store_true")
     a = ap.parse_args()
     if a.worker:

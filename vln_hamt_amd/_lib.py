@@ -108,6 +108,7 @@ SIGNATURES = {
     "hamt_gemm": [C.POINTER(GemmDesc), vp, vp, vp, vp, vp, vp],
     "hamt_gemm_ksplit": [C.POINTER(GemmDesc)],
     "hamt_gemm_ws": [C.POINTER(GemmDesc), vp, vp, vp, vp, vp, vp, sz, vp],
+    "hamt_gemm_plan": [C.POINTER(GemmDesc), sz, C.c_char_p, sz],
     "hamt_cast_pad_bf16": [i32, i32, i32, i32, vp, i32, vp, i32, vp],
     "hamt_cast_pad_bf16_dropout": [i32, i32, i32, vp, i32, vp, i32, f32, u32, vp, vp],
     "hamt_cast_transpose": [i32, i32, vp, i32, i32, vp, i32, i32, vp],
@@ -235,6 +236,14 @@ def last_kernel() -> str:
     buf = C.create_string_buffer(160)
     load().hamt_last_kernel(buf, 160)
     return buf.value.decode(errors="replace")
+
+
+def gemm_plan(desc: GemmDesc, ws_bytes=None):
+    """(K slices, kernel name) hamt_gemm_ws would use for `desc` with `ws_bytes` of workspace (None: as much as it asks for); no launch"""
+    buf = C.create_string_buffer(160)
+    ks = load().hamt_gemm_plan(C.byref(desc), sz(-1).value if ws_bytes is None else ws_bytes, buf, 160)
+    check(min(ks, 0), "hamt_gemm_plan")
+    return ks, buf.value.decode(errors="replace")
 
 
 def workspace_bytes(op: int, *shape) -> int:

@@ -14,6 +14,7 @@
 // Replaces every nn.Linear forward/backward on the reference path (vilmodel.py:97-99, 140, 169,
 // 182, 263, 284, 323-325, 497-498, 549-558; pretrain_cmt.py:16-68).
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -437,10 +438,8 @@ extern "C" int hamt_smallk_wgrad(int M, int N, int K, const float* dy, int lddy,
   return HAMT_OK;
 }
 
-bool hamt_gemm_fast_eligible(const hamt_gemm_desc* d, const void* A, const void* B);
-int hamt_gemm_fast_ksplit(const hamt_gemm_desc* d, size_t ws_bytes);
-void hamt_gemm_fast_launch(const hamt_gemm_desc* d, const void* A, const void* B, void* C, const float* bias, void* aux, float* ws,
-                           size_t ws_bytes, hipStream_t s);
+void hamt_gemm_fast_launch(const hamt_gemm_desc* d, const GemmPlan& p, const void* A, const void* B, void* C, const float* bias, void* aux,
+                           float* ws, hipStream_t s);      // gemm_fast.hip
 
 void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumulate, hipStream_t s) {
   if (N % 4 == 0 && (((uintptr_t)ws | (uintptr_t)out) % 16) == 0) {
@@ -452,11 +451,22 @@ void hamt_reduce_partials(int R, int N, const float* ws, float* out, int accumul
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, s, R, N, ws, out, accumulate);
 }
 
-extern "C" int hamt_gemm_ksplit(const hamt_gemm_desc* d) {
-  if (!d || d->prec != HAMT_PREC_BF16 || d->dtype_a != HAMT_BF16 || d->dtype_b != HAMT_BF16 || (d->a_kmajor && !d->b_kmajor) ||
-      d->K < 64 || d->K % 64)
-    return 1;
-  return hamt_gemm_fast_ksplit(d, (size_t)-1);
+static const GemmTuning& gemm_tuning() {      // the dispatch switches: read from the environment once per process, here only
+  static const GemmTuning t = [] {
+    auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+    return GemmTuning{getenv("HAMT_NO_FAST") != nullptr, num("HAMT_FAST_BM", 0), num("HAMT_KS", 0), num("HAMT_KG", 0), num("HAMT_Q4", -1),
+                      num("HAMT_P8", -1), num("HAMT_P8_BN", 0)};
+  }();
+  return t;
+}
+
+extern "C" int hamt_gemm_ksplit(const hamt_gemm_desc* d) { return d ? gemm_plan(*d, (size_t)-1, gemm_tuning()).ksplit : 1; }
+
+extern "C" int hamt_gemm_plan(const hamt_gemm_desc* d, size_t ws_bytes, char* name, size_t n) {
+  HAMT_CHECK_ARG(d && (name || n == 0), "hamt_gemm_plan: null pointer");
+  const GemmPlan p = gemm_plan(*d, ws_bytes, gemm_tuning());
+  if (n) gemm_plan_name(p, name, n);
+  return p.ksplit;
 }
 
 extern "C" int hamt_gemm(const hamt_gemm_desc* d, const void* A, const void* B, void* C, const float* bias, void* aux,
@@ -480,20 +490,23 @@ extern "C" int hamt_gemm_ws(const hamt_gemm_desc* d, const void* A, const void* 
   if (aux && d->dtype_aux == HAMT_U8G)
     HAMT_CHECK_ARG((d->epilogue & (HAMT_EPI_GELU_GRAD | HAMT_EPI_MUL_AUX)) && !(d->epilogue & (HAMT_EPI_SAVE_PRE | HAMT_EPI_MUL_DGELU | HAMT_EPI_MUL_DRELU | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT)),
                    "hamt_gemm: a HAMT_U8G aux is the gelu' image of HAMT_EPI_GELU_GRAD (without dropout) / HAMT_EPI_MUL_AUX only");
+  const GemmPlan p = gemm_plan(*d, ws ? ws_bytes : 0, gemm_tuning());
+  const bool fast = p.family != GEMM_F32 && p.family != GEMM_BF16;   // bf16 x bf16, K % 64 == 0, ... (gemm_plan.h: gemm_fast_eligible)
   if (d->epilogue & HAMT_EPI_DROPOUT) {
     HAMT_CHECK_ARG(d->rng && d->p_drop >= 0.0f && d->p_drop < 1.0f, "hamt_gemm: EPI_DROPOUT needs rng and 0 <= p_drop < 1");
-    HAMT_CHECK_ARG(getenv("HAMT_NO_FAST") == nullptr && hamt_gemm_fast_eligible(d, A, B), "hamt_gemm: EPI_DROPOUT is implemented by the bf16 MFMA path only (bf16 operands, K %% 64 == 0)");
+    HAMT_CHECK_ARG(fast, "hamt_gemm: EPI_DROPOUT is implemented by the bf16 MFMA path only (bf16 operands, K %% 64 == 0)");
   }
   const int ka = (d->ka_rows > 0 && d->ka_rows < d->K) ? d->ka_rows : d->K, kb = (d->kb_rows > 0 && d->kb_rows < d->K) ? d->kb_rows : d->K;
   GemmArgs g{d->M, d->N, d->K, d->lda, d->ldb, ka, kb, d->ldc, d->ldaux, d->dtype_c, d->dtype_aux, d->epilogue, d->alpha, A, B, C, bias, aux};
   hipStream_t s = as_stream(stream);
-  static const bool no_fast = getenv("HAMT_NO_FAST") != nullptr;
-  if (!no_fast && hamt_gemm_fast_eligible(d, A, B)) {  // bf16 x bf16, K-contiguous operands, K % 64 == 0
-    hamt_gemm_fast_launch(d, A, B, C, bias, aux, (float*)ws, ws_bytes, s);
+  char name[160];
+  gemm_plan_name(p, name, sizeof(name));
+  hamt_set_last_kernel("%s", name);
+  if (fast) {
+    hamt_gemm_fast_launch(d, p, A, B, C, bias, aux, (float*)ws, s);
     HAMT_CHECK_LAUNCH("hamt_gemm(fast)");
     return HAMT_OK;
   }
-  hamt_set_last_kernel(d->prec == HAMT_PREC_F32 ? "gemm_f32_kernel<%s, %s>" : "gemm_bf16_kernel<%s, %s, ...>", d->a_kmajor ? "true" : "false", d->b_kmajor ? "true" : "false");
   if (d->prec == HAMT_PREC_F32) {
     HAMT_CHECK_ARG(d->dtype_a == HAMT_F32 && d->dtype_b == HAMT_F32, "hamt_gemm: PREC_F32 needs fp32 operands");
     int tiles = ((d->M + F_BM - 1) / F_BM) * ((d->N + F_BN - 1) / F_BN);

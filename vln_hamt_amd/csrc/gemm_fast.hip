@@ -25,11 +25,12 @@
 //     one XCD so that its operand panels cross the fabric once, bias sums fused in.
 #include "common.h"
 #include "gemm_args.h"
+#include "gemm_plan.h"
 #include <algorithm>
 #include <type_traits>
 #include <vector>
 
-bool hamt_gemm_q4_launch(const GemmArgsF& g, bool b_kmajor, hipStream_t s);      // gemm_q4.hip: the 128-square tile with a four-deep operand ring
+void hamt_gemm_q4_launch(const GemmArgsF& g, int epi, bool b_kmajor, hipStream_t s);      // gemm_q4.hip: the 128-square tile with a four-deep operand ring
 
 
 #ifdef HAMT_PROF   // cycle accounting of the main loop (tools/gemm_prof.py builds a private copy with -DHAMT_PROF)
@@ -962,228 +963,76 @@ __global__ __launch_bounds__(512) void wgrad_grouped_p8_kernel(const WgradProb* 
   p8_tile<-2, true, true, true>(g, (local / tiles_n) * 256, (local % tiles_n) * 256, q.db, q.flags & 2);
 }
 
-template <bool A_KM, bool B_KM, int NB = 4>
-bool launch_p8(const GemmArgsF& g, hipStream_t s) {
+static_assert(BN == PLAN_BN && BK == PLAN_BK, "gemm_plan.h counts tiles of these kernels");
+
+// The launch switches: one case per compiled epilogue of the family (the lists of gemm_plan.h), taken on the epilogue the plan decided.
+template <bool B_KM, int NB>
+void launch_p8(const GemmArgsF& g, int epi, hipStream_t s) {
   const dim3 grid(((g.M + 255) / 256) * ((g.N + 64 * NB - 1) / (64 * NB)));
-  const int e = g.epi;
-#define HAMT_L(E) do { hipLaunchKernelGGL((gemm_p8_kernel<E, A_KM, B_KM, NB>), grid, dim3(512), 0, s, g); \
-                    hamt_set_last_kernel("gemm_p8_kernel<%d, %s, %s, %d>", (int)(E), A_KM ? "true" : "false", B_KM ? "true" : "false", NB); } while (0)
-  if (e == 0) HAMT_L(0);
-  else if (e == HAMT_EPI_BIAS) HAMT_L(HAMT_EPI_BIAS);
-  else if (e == HAMT_EPI_ACCUM) HAMT_L(HAMT_EPI_ACCUM);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD);
-  else if (e == HAMT_EPI_MUL_AUX) HAMT_L(HAMT_EPI_MUL_AUX);
-  else if constexpr (!B_KM && NB == 4) {      // forward-only epilogues (the pre-LN ViT blocks: residual add / dropout in the epilogue)
-    if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX);
-    else if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT);
-    else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT);
-    else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU);
-    else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_DROPOUT);
-    else return false;
-  } else return false;
+#define HAMT_L(E) case (E): hipLaunchKernelGGL((gemm_p8_kernel<(E), false, B_KM, NB>), grid, dim3(512), 0, s, g); break;
+  switch (epi) {
+    HAMT_EPIS_P8(HAMT_L)
+    default:
+      if constexpr (!B_KM && NB == 4) switch (epi) { HAMT_EPIS_P8_FWD(HAMT_L) }
+  }
 #undef HAMT_L
-  return true;
 }
 
-template <bool A_KM, bool B_KM>
-bool launch_256(const GemmArgsF& g, hipStream_t s) {
+template <bool B_KM>
+void launch_256(const GemmArgsF& g, int epi, hipStream_t s) {
   const dim3 grid(((g.M + 255) / 256) * ((g.N + 255) / 256));
-  const int e = g.epi;
-#define HAMT_L(E) do { hipLaunchKernelGGL((gemm_fast256_kernel<E, A_KM, B_KM>), grid, dim3(512), 0, s, g); \
-                    hamt_set_last_kernel("gemm_fast256_kernel<%d, %s, %s>", (int)(E), A_KM ? "true" : "false", B_KM ? "true" : "false"); } while (0)
-  if (e == 0) HAMT_L(0);
-  else if (e == HAMT_EPI_BIAS) HAMT_L(HAMT_EPI_BIAS);
-  else if (e == HAMT_EPI_ACCUM) HAMT_L(HAMT_EPI_ACCUM);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD);
-  else if (e == HAMT_EPI_MUL_AUX) HAMT_L(HAMT_EPI_MUL_AUX);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT);
-  else return false;
+#define HAMT_L(E) case (E): hipLaunchKernelGGL((gemm_fast256_kernel<(E), false, B_KM>), grid, dim3(512), 0, s, g); break;
+  switch (epi) { HAMT_EPIS_256(HAMT_L) }
 #undef HAMT_L
-  return true;
 }
 
-template <int BM, bool A_KM, bool B_KM, int NST = 2>
-void launch_bm(const GemmArgsF& g, dim3 grid, hipStream_t s) {
-  const int e = g.epi;
-#define HAMT_L(E) do { hipLaunchKernelGGL((gemm_fast_kernel<BM, E, A_KM, B_KM, NST>), grid, dim3(256), 0, s, g); \
-                    hamt_set_last_kernel(NST == 2 ? "gemm_fast_kernel<%d, %d, %s, %s>" : "gemm_fast_kernel<%d, %d, %s, %s, %d>", BM, (int)(E), A_KM ? "true" : "false", B_KM ? "true" : "false", NST); } while (0)
-  if (e == 0) HAMT_L(0);
-  else if (e == HAMT_EPI_BIAS) HAMT_L(HAMT_EPI_BIAS);
-  else if (e == HAMT_EPI_ACCUM) HAMT_L(HAMT_EPI_ACCUM);
-  else if constexpr (BM == 32) launch_bm<64, A_KM, B_KM, NST>(g, dim3(((g.M + 63) / 64) * ((g.N + BN - 1) / BN), grid.y), s);   // 32-row tiles: narrow-output epilogues only
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_SAVE_PRE)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_SAVE_PRE);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_RELU)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_RELU);
-  else if (e == HAMT_EPI_MUL_DGELU) HAMT_L(HAMT_EPI_MUL_DGELU);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD);
-  else if (e == HAMT_EPI_MUL_AUX) HAMT_L(HAMT_EPI_MUL_AUX);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_ADD_AUX | HAMT_EPI_DROPOUT);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU_GRAD | HAMT_EPI_DROPOUT);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU);
-  else if (e == (HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_DROPOUT)) HAMT_L(HAMT_EPI_BIAS | HAMT_EPI_GELU | HAMT_EPI_DROPOUT);
-  else HAMT_L(-1);
+template <int BM, bool A_KM, bool B_KM>
+void launch_bm(const GemmArgsF& g, int epi, hipStream_t s) {
+  const dim3 grid(((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN), g.ksplit);
+#define HAMT_L(E) case (E): hipLaunchKernelGGL((gemm_fast_kernel<BM, (E), A_KM, B_KM>), grid, dim3(256), 0, s, g); break;
+  if constexpr (BM == 32) switch (epi) { HAMT_EPIS_NARROW(HAMT_L) }
+  else switch (epi) { HAMT_EPIS_FAST(HAMT_L) HAMT_L(-1) }
 #undef HAMT_L
+}
+
+template <int BM, int G, int D>
+void launch_kg(const GemmArgsF& g, bool b_kmajor, hipStream_t s) {
+  const dim3 grid(((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN));
+  if (b_kmajor) hipLaunchKernelGGL((gemm_kg_kernel<BM, G, D, true>), grid, dim3(256 * G), 0, s, g);
+  else hipLaunchKernelGGL((gemm_kg_kernel<BM, G, D, false>), grid, dim3(256 * G), 0, s, g);
 }
 
 }  // namespace
 
-// Layouts: NT (forward), NN (dgrad: B = W stored [K][N]), TN (wgrad: A = dY stored [K][M], B = X stored [K][N]).
-// K-contiguous operands need K % 64 == 0 (the caller pads with zeros); K-strided operands are clamped to row K-1,
-// so for a ragged K the OTHER operand must hold zeros there (NN: zero-padded dY columns; TN: zero-padded dY rows).
-bool hamt_gemm_fast_eligible(const hamt_gemm_desc* d, const void* A, const void* B) {
-  if (d->prec != HAMT_PREC_BF16 || d->dtype_a != HAMT_BF16 || d->dtype_b != HAMT_BF16) return false;
-  if (d->a_kmajor && !d->b_kmajor) return false;
-  if (d->K < 64 || d->M < 1 || d->N < 1) return false;
-  if ((!d->a_kmajor || !d->b_kmajor) && d->K % 64 != 0) return false;
-  if (d->a_kmajor && d->K % 64 != 0) return false;   // TN: the caller pads the reduction rows of A with zeros
-  if (d->lda % 8 || d->ldb % 8 || ((uintptr_t)A % 16) || ((uintptr_t)B % 16)) return false;
-  {   // the DMA pieces address their operand with 32-bit byte offsets from its base
-    const double a_bytes = 2.0 * (d->a_kmajor ? (double)d->K : (double)d->M) * d->lda, b_bytes = 2.0 * (d->b_kmajor ? (double)d->K : (double)d->N) * d->ldb;
-    if (a_bytes >= 4294967296.0 || b_bytes >= 4294967296.0) return false;
-  }
-  if (d->a_kmajor && d->lda < 64) return false;
-  if (d->b_kmajor && d->ldb < 128) return false;
-  return true;
-}
-
-// K groups inside the workgroup (gemm_kg_kernel) instead of plain tiles / split-K: when the whole output is at most one round
-// of workgroups of that kernel and the reduction is long enough to amortise the extra LDS pass.  Returns 100 * tile rows +
-// 10 * groups + ring depth, or 0.  Measured (tools/ksplit_sweep.py, B = 16 shapes, us): 1280x768x3072 29.4 -> 16.7,
-// x2304 17.6 -> 14.5, 1968x768x3072 29.9 -> 22.2, x2304 22.9 -> 17.8; no gain once the plain tiles fill the chip (B = 64).
-static int kg_variant(const hamt_gemm_desc* d) {
-  static const int force = getenv("HAMT_KG") ? atoi(getenv("HAMT_KG")) : 0;   // 1 = never, > 1 = always this variant
-  if (d->a_kmajor || force == 1) return 0;
-  if (force) return force;
-  const int nk = d->K / BK;
-  if (nk < 12 || d->N > 1024) return 0;
-  const long tn = (d->N + 127) / 128, t32 = (long)((d->M + 31) / 32) * tn, t64 = (long)((d->M + 63) / 64) * tn;
-  // a VERY long reduction over a small output (the MLM decoder's dgrad: 768 x 768 x 30 528 at B = 64): 144 workgroups walking 477
-  // k-tiles each took 157 us in the step (profiles/r04_*); split-K over the grid (10 slices of 128-row tiles, ~360 workgroups, the
-  // partial tiles are 24 MB) is the better form there -- when the caller can take it (plain / accumulate epilogue, fp32 C)
-  if (nk >= 192 && t64 <= 128 && !(d->epilogue & ~HAMT_EPI_ACCUM) && d->dtype_c == HAMT_F32 && d->ldc == d->N) return 0;
-  if (t32 <= 256) return 3224;
-  if (t64 <= 256 && nk >= 24) return 6432;
-  // one 128-row tile per CU, two groups (B = 64 text / vision streams: 5120x768x3072 41.2 -> 35.3 us, 2752x768x2304 27.7 -> 24.2)
-  const long t128 = (long)((d->M + 127) / 128) * tn;
-  if (t128 <= 256 && nk >= 36) return 12822;
-  return 0;
-}
-
-// K slices to use for this problem given `ws_bytes` of workspace (1 = no split).
-int hamt_gemm_fast_ksplit(const hamt_gemm_desc* d, size_t ws_bytes) {
-  if (d->epilogue & ~HAMT_EPI_ACCUM) return 1;
-  if (d->dtype_c != HAMT_F32 || d->ldc != d->N) return 1;
-  static const int force_bm = getenv("HAMT_FAST_BM") ? atoi(getenv("HAMT_FAST_BM")) : 0;
-  static const int force = getenv("HAMT_KS") ? atoi(getenv("HAMT_KS")) : 0;
-  if (!force_bm && !force && kg_variant(d)) return 1;
-  const long tiles = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
-  const int nk = d->K / BK;
-  int s;
-  if (force) s = force > nk ? nk : force;
-  else {
-    if (tiles >= 192 || nk < 16) return 1;
-    s = (int)(384 / tiles);
-    if (s > nk / 8) s = nk / 8;
-    if (s > 16) s = 16;
-  }
-  while (s > 1 && (size_t)s * d->M * d->N * 4 > ws_bytes) --s;
-  return s < 2 ? 1 : s;
-}
-
-// 256-square tiles (8 waves, one workgroup per CU, operands re-used twice as often per DMA piece and LDS read): when the
-// reduction is long, the grid is 0.8 .. 1 tile per CU or at least 3 per CU, and the K-strided operand rows are wide enough.
-static bool use256(const hamt_gemm_desc* d, int force_bm) {
-  if (d->b_kmajor && d->ldb < 256) return false;
-  if (force_bm) return force_bm == 256;
-  if (d->K < 2048) return false;   // one workgroup per CU exposes the tile's prologue and store tail: long reductions only
-  const long t = (long)((d->M + 255) / 256) * ((d->N + 255) / 256);   // (measured: 5120x3072x768 35.7 us with 128-row tiles, 40 with 256)
-  return (t >= 208 && t <= 256) || t >= 768;
-}
-
-void hamt_gemm_fast_launch(const hamt_gemm_desc* d, const void* A, const void* B, void* C, const float* bias, void* aux,
-                           float* ws, size_t ws_bytes, hipStream_t s) {
+// Launches the kernel `p` names (gemm_plan.h: the whole choice is made there) and, for a split reduction, the sum of the partial tiles.
+void hamt_gemm_fast_launch(const hamt_gemm_desc* d, const GemmPlan& p, const void* A, const void* B, void* C, const float* bias, void* aux,
+                           float* ws, hipStream_t s) {
   GemmArgsF g{d->M, d->N, d->K, d->lda, d->ldb, d->ldc, d->ldaux, d->dtype_c, d->dtype_aux, d->epilogue, d->alpha,
-              (const bf16_t*)A, (const bf16_t*)B, C, bias, aux, 1, nullptr,
+              (const bf16_t*)A, (const bf16_t*)B, C, bias, aux, p.ksplit, p.ksplit > 1 ? ws : nullptr,
               ((d->ka_rows > 0 && d->ka_rows < d->K) ? d->ka_rows : d->K) - 1, ((d->kb_rows > 0 && d->kb_rows < d->K) ? d->kb_rows : d->K) - 1,
               d->p_drop, d->call_id, d->rng};
-  const int ks = ws ? hamt_gemm_fast_ksplit(d, ws_bytes) : 1;
-  const long t128 = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
-  static const int force_bm = getenv("HAMT_FAST_BM") ? atoi(getenv("HAMT_FAST_BM")) : 0;
-  // Tile height.  The ring is 2 deep (64 / 48 KiB), so 2 workgroups of 128 rows or 3 of 64 rows share a CU and one's
-  // prologue / epilogue / DMA issue overlaps another's MFMA loop (measured: 4096^3 894 TFLOP/s vs 692 with a 3-deep
-  // ring at one workgroup per CU).  128-row tiles do ~1.4x the flops per LDS byte, 64-row tiles fill the chip when the
-  // grid is small: pick the one with the lower (rounds of resident workgroups) x (time per tile) estimate.
-  const long t64 = (long)((d->M + 63) / 64) * ((d->N + 127) / 128);
-  const long r128 = (t128 * ks + 511) / 512, r64 = (t64 * ks + 767) / 768;
-  const bool bm64 = force_bm ? force_bm == 64 : (t128 * ks < 1024 && r64 * 25 < r128 * 36);   // tile-time ratio 1 : 1.44
-  g.ksplit = ks;
-  g.part = ks > 1 ? ws : nullptr;
-  const dim3 g64(((d->M + 63) / 64) * ((d->N + BN - 1) / BN), ks), g128(((d->M + 127) / 128) * ((d->N + BN - 1) / BN), ks);
-  // The 128-square tile with the four-deep ring (gemm_q4.hip): narrow outputs whose 128-square tiling is about one round of the chip.
-  // HAMT_Q4 = 0 / 1: never / whenever the kernel can run the problem (tuning and tests).
-  static const int q4 = getenv("HAMT_Q4") ? atoi(getenv("HAMT_Q4")) : -1;
-  if (ks == 1 && q4 != 0 && !force_bm && !d->a_kmajor) {
-    // (measured, profiles/r05_q4_probe.txt: equal to the K-group / 64-row tiles on warm operands, 13 - 20 % ahead on cold ones -- the step's
-    // case -- at 240 and at 132 tiles; behind them below ~100 tiles, behind the 256-row tiles beyond one round and on N = 1536)
-    const bool pick = q4 == 1 || (d->N <= 1024 && d->K >= 192 && t128 >= 120 && t128 <= 256);
-    if (pick && hamt_gemm_q4_launch(g, d->b_kmajor != 0, s)) return;
-  }
-  // 256-square two-phase kernel (one 8-wave workgroup per CU): by estimated time.  Measured on MI355X (tools/gemm_sweep.py,
-  // tools/p8_probe.py): a p8 tile costs ~6 us + 1.55 us per k-tile whatever the grid, the 64/128-row tiles run the
-  // step's shapes at ~620 TFLOP/s.  HAMT_P8=0 / 1 = never / whenever eligible.
-  static const int p8 = getenv("HAMT_P8") ? atoi(getenv("HAMT_P8")) : -1;
-  if (ks == 1 && p8 != 0 && !force_bm && d->K >= 128 && !d->a_kmajor && (!d->b_kmajor || d->ldb >= 256)) {
-    const long t256 = (long)((d->M + 255) / 256) * ((d->N + 255) / 256), t192 = (long)((d->M + 255) / 256) * ((d->N + 191) / 192);
-    const double t_p8 = (double)((t256 + 255) / 256) * (6.0 + 1.55 * (d->K / BK));
-    // 256 x 192 tiles: 3/4 of the MFMA work and 7/8 of the operand bytes of a 256-square tile per k-tile -- but measured 0.92-0.94 of
-    // its TIME at K = 768 .. 3072 (tools/gemm_bench.py with HAMT_P8_BN = 192 / 256: a tile's life is prologue, barriers and the
-    // store tail as much as MFMA issue): worth it only where it does not add a round -- 5120 x 2304 x 768: 180 tiles -> 240, one
-    // round either way, 27.6 -> 26.0 us; 11520 x 768 x 3072: 65.2 -> 59.8; 11520 x 768 x 2304 (NN, acc): 55.3 -> 50.9.  The FFN-1
-    // epilogue (gelu + gelu', two stores per tile) measured 4 % SLOWER with the narrow tile at 720 tiles: kept on 256 columns there.
-    static const int bn_force = getenv("HAMT_P8_BN") ? atoi(getenv("HAMT_P8_BN")) : 0;      // 192 / 256: tuning and tests
-    const double t_p8n = (double)((t192 + 255) / 256) * (6.0 + 1.44 * (d->K / BK));
-    const bool n192 = bn_force ? bn_force == 192 : (t_p8n < 0.97 * t_p8 && !((d->epilogue & HAMT_EPI_GELU_GRAD) && t192 > 512));
-    const double t_small = 2.0 * d->M * d->N * d->K / 620e6;
-    if (p8 == 1 || (n192 ? t_p8n : t_p8) < 0.95 * t_small) {
-      bool ok = false;
-      if (n192) ok = !d->b_kmajor ? launch_p8<false, false, 3>(g, s) : launch_p8<false, true, 3>(g, s);
-      if (!ok) ok = !d->b_kmajor ? launch_p8<false, false>(g, s) : launch_p8<false, true>(g, s);
-      if (ok) return;
-    }
-  }
-  if (ks == 1 && !force_bm) {
-    const int kg = kg_variant(d);
-    if (kg) {
-      const int bm = kg / 100, G = (kg / 10) % 10, D = kg % 10;
-      const dim3 grid(((d->M + bm - 1) / bm) * ((d->N + BN - 1) / BN));
-#define HAMT_KGL(BM_, G_, D_) do { if (d->b_kmajor) hipLaunchKernelGGL((gemm_kg_kernel<BM_, G_, D_, true>), grid, dim3(256 * G_), 0, s, g); \
-                               else hipLaunchKernelGGL((gemm_kg_kernel<BM_, G_, D_, false>), grid, dim3(256 * G_), 0, s, g); \
-                               hamt_set_last_kernel("gemm_kg_kernel<%d, %d, %d, %s>", BM_, G_, D_, d->b_kmajor ? "true" : "false"); } while (0)
-      if (bm == 32 && G == 2 && D == 3) HAMT_KGL(32, 2, 3); else if (bm == 32 && G == 3) HAMT_KGL(32, 3, 2);
-      else if (bm == 32) HAMT_KGL(32, 2, 4); else if (bm == 128) HAMT_KGL(128, 2, 2); else if (G == 2) HAMT_KGL(64, 2, 3); else HAMT_KGL(64, 3, 2);
+  switch (p.family) {
+    case GEMM_Q4: hamt_gemm_q4_launch(g, p.epi, p.b_kmajor, s); break;
+    case GEMM_P8:
+      if (p.p8_nb == 3) { if (p.b_kmajor) launch_p8<true, 3>(g, p.epi, s); else launch_p8<false, 3>(g, p.epi, s); }
+      else { if (p.b_kmajor) launch_p8<true, 4>(g, p.epi, s); else launch_p8<false, 4>(g, p.epi, s); }
+      break;
+    case GEMM_KG:
+#define HAMT_KGL(BM_, G_, D_) if (p.tile_rows == BM_ && p.kg_groups == G_ && p.kg_depth == D_) launch_kg<BM_, G_, D_>(g, p.b_kmajor, s);
+      HAMT_KG_VARIANTS(HAMT_KGL)
 #undef HAMT_KGL
-      return;
-    }
-  }
-  if (ks == 1 && use256(d, force_bm)) {
-    const bool ok = !d->a_kmajor ? (!d->b_kmajor ? launch_256<false, false>(g, s) : launch_256<false, true>(g, s)) : false;
-    if (ok) return;
-  }
-  // 32-row tiles: for grids so small (the B = 16 shapes: 1280 x 768 outputs are 120 tiles of 64 rows) that 64-row tiles leave every
-  // SIMD with at most one wave, which then issues its DMA pieces, reads its fragments and multiplies strictly in turn
-  const long t32 = (long)((d->M + 31) / 32) * ((d->N + 127) / 128);
-  const bool bm32 = force_bm ? force_bm == 32 : (bm64 && ks == 1 && t64 <= 160 && d->K <= 1024);
-  const dim3 g32(((d->M + 31) / 32) * ((d->N + BN - 1) / BN), ks);
-  (void)t32;
+      break;
+    case GEMM_FAST256: if (p.b_kmajor) launch_256<true>(g, p.epi, s); else launch_256<false>(g, p.epi, s); break;
+    default:      // GEMM_FAST (the generic kernels never come here)
 #define HAMT_BMST(AK, BK_) do { \
-    if (bm32) launch_bm<32, AK, BK_>(g, g32, s); else if (bm64) launch_bm<64, AK, BK_>(g, g64, s); else launch_bm<128, AK, BK_>(g, g128, s); } while (0)
-  if (!d->a_kmajor && !d->b_kmajor) HAMT_BMST(false, false);
-  else if (!d->a_kmajor) HAMT_BMST(false, true);
+    if (p.tile_rows == 32) launch_bm<32, AK, BK_>(g, p.epi, s); else if (p.tile_rows == 64) launch_bm<64, AK, BK_>(g, p.epi, s); else launch_bm<128, AK, BK_>(g, p.epi, s); } while (0)
+      if (!p.a_kmajor && !p.b_kmajor) HAMT_BMST(false, false);
+      else if (!p.a_kmajor) HAMT_BMST(false, true);
 #undef HAMT_BMST
-  else { if (bm64 && d->lda >= 64) launch_bm<64, true, true>(g, g64, s); else launch_bm<128, true, true>(g, g128, s); }
-  if (ks > 1) hamt_reduce_partials(ks, d->M * d->N, ws, (float*)C, (d->epilogue & HAMT_EPI_ACCUM) ? 1 : 0, s);
+      else if (p.tile_rows == 64) launch_bm<64, true, true>(g, p.epi, s);
+      else launch_bm<128, true, true>(g, p.epi, s);
+      if (p.ksplit > 1) hamt_reduce_partials(p.ksplit, d->M * d->N, ws, (float*)C, (d->epilogue & HAMT_EPI_ACCUM) ? 1 : 0, s);
+  }
 }
 
 extern "C" int hamt_cast_transpose(int R, int C, const void* x, int ldx, int dtype_x, void* y, int ldy, int Rpad, void* stream) {

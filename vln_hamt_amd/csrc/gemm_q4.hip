@@ -23,6 +23,7 @@
 // hipBLASLt's included, sits at ~0.55 us per k-tile (~900 cycles at the ~1.65 GHz the chip holds under this load; 16 bare MFMAs issue in ~350).
 #include "common.h"
 #include "gemm_args.h"
+#include "gemm_plan.h"
 #include <type_traits>
 
 namespace {
@@ -159,26 +160,16 @@ __global__ __launch_bounds__(512) void gemm_q4_kernel(GemmArgsF g) {
 }
 
 
-template <bool B_KM>
-bool launch_q4(const GemmArgsF& g, hipStream_t s) {
-  const dim3 grid(((g.M + 127) / 128) * ((g.N + 127) / 128));
-  const int e = g.epi;
-#define HAMT_L(E) do { hipLaunchKernelGGL((gemm_q4_kernel<E, B_KM>), grid, dim3(512), 0, s, g); \
-                    hamt_set_last_kernel("gemm_q4_kernel<%d, %s>", (int)(E), B_KM ? "true" : "false"); } while (0)
-  if (e == 0) HAMT_L(0);
-  else if (e == HAMT_EPI_BIAS) HAMT_L(HAMT_EPI_BIAS);
-  else if (e == HAMT_EPI_ACCUM) HAMT_L(HAMT_EPI_ACCUM);
-  else return false;
-#undef HAMT_L
-  return true;
-}
-
 }  // namespace
 
-// true: launched.  The caller (hamt_gemm_fast_launch) has checked the fast path's operand contract (bf16, K % 64 == 0, alignment, 32-bit
-// offsets) and decides WHEN this tile is the right one; here only what the kernel itself needs.
-bool hamt_gemm_q4_launch(const GemmArgsF& g, bool b_kmajor, hipStream_t s) {
-  if (g.K < 3 * BK || g.ksplit > 1) return false;
-  if (b_kmajor && g.ldb < 128) return false;
-  return b_kmajor ? launch_q4<true>(g, s) : launch_q4<false>(g, s);
+// The caller (hamt_gemm_fast_launch) launches what gemm_plan decided: WHEN this tile is the right one, what the kernel itself needs
+// (>= 3 k-tiles, no split) and the epilogue it is compiled for are all settled there.
+void hamt_gemm_q4_launch(const GemmArgsF& g, int epi, bool b_kmajor, hipStream_t s) {
+  const dim3 grid(((g.M + 127) / 128) * ((g.N + 127) / 128));
+#define HAMT_L(E) case (E): \
+    if (b_kmajor) hipLaunchKernelGGL((gemm_q4_kernel<(E), true>), grid, dim3(512), 0, s, g); \
+    else hipLaunchKernelGGL((gemm_q4_kernel<(E), false>), grid, dim3(512), 0, s, g); \
+    break;
+  switch (epi) { HAMT_EPIS_NARROW(HAMT_L) }
+#undef HAMT_L
 }
