@@ -781,6 +781,21 @@ int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p16, float* 
                       const float* hyp, const float* rl, int nparams, float* partials, float* stats, const float* gnorm_sq,
                       float max_norm, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
                       int zero_grad, void* stream);
+/* torch.optim's AdamW / Adam / RMSprop (momentum 0, not centered) / SGD (momentum 0): the finetune agents' optimisers
+ * (finetune_src/r2r/agent_cmt.py:62-77), one launch over the whole arena with hamt_adamw_table's `ends` table, flags, clip and sweep.
+ * Per element, gg = g * min(1, max_norm / (sqrt(*gnorm_sq) + 1e-6)) (1 when gnorm_sq is NULL or max_norm <= 0), t the parameter's own step:
+ *   ADAMW    p *= 1 - lr*wd;  m = b1 m + (1-b1) gg;  v = b2 v + (1-b2) gg^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
+ *   ADAM     gg += wd*p;  then ADAMW's moments and update, without the multiplicative decay
+ *   RMSPROP  gg += wd*p;  v = alpha v + (1-alpha) gg^2 (alpha is passed as beta2);  p -= lr * gg / (sqrt(v) + eps);  m is not touched
+ *   SGD      gg += wd*p;  p -= lr * gg;  m and v are not touched
+ * hyp (DEVICE, nparams x 4 floats): {lr, lr / (1-b1^t), weight_decay, active} -- hamt_adamw_table's layout and flags, the table
+ *   hamt_sumsq_table reads.  aux (DEVICE, nparams x 4 floats): {1 / sqrt(1-b2^t), 1 - lr*wd, 0, 0}.  The host forms every entry in
+ *   float64 and rounds once.  An arena its rule does not touch may be NULL; a NULL arena the rule needs, an unknown rule, NULL
+ *   ends / hyp / aux and n % 4 != 0 are HAMT_ERR_ARG and nothing is launched.  p16 may be NULL. */
+typedef enum { HAMT_OPT_ADAMW = 0, HAMT_OPT_ADAM = 1, HAMT_OPT_RMSPROP = 2, HAMT_OPT_SGD = 3 } hamt_opt_rule;
+int hamt_optim_table(int rule, size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
+                     const float* aux, int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
+                     int zero_grad, void* stream);
 /* g *= min(1, max_norm / (sqrt(*gnorm_sq) + 1e-6))  -- standalone clip for torch-optimiser users */
 int hamt_clip_scale(size_t n, float* g, const float* gnorm_sq, float max_norm, void* stream);
 

@@ -17,6 +17,7 @@ PREC_BF16, PREC_F32 = 0, 1
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_ACCUM, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_SAVE_PRE = 1, 2, 4, 8, 16, 32, 64
 EPI_GELU_GRAD, EPI_MUL_AUX, EPI_ADD_AUX, EPI_DROPOUT = 128, 256, 512, 1024
 SUMSQ_SPARSE = 2            # HAMT_SUMSQ_SPARSE (hamt_sumsq_table's `accumulate`, bit 1)
+OPT_ADAMW, OPT_ADAM, OPT_RMSPROP, OPT_SGD = 0, 1, 2, 3      # hamt_opt_rule (hamt_optim_table)
 
 vp, i32, u32, f32, sz = C.c_void_p, C.c_int, C.c_uint32, C.c_float, C.c_size_t
 
@@ -190,6 +191,7 @@ SIGNATURES = {
     "hamt_adamw_table": [sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_adamw_table_range": [sz, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_ralamb_table": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp],
+    "hamt_optim_table": [i32, sz, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_clip_scale": [sz, vp, vp, f32, vp],
     "hamt_rng_advance": [vp, vp],
 }

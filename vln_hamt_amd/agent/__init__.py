@@ -1,9 +1,10 @@
 """The part of a finetune rollout every agent of the reference shares (R2R, R2R-back, CVDN, REVERIE's action side): the per-step action
 choice and losses on the device, and (nav_graph) what they read from the navigation graph: teacher lookup, back-track mask, reward
 shaping, metrics; REVERIE's own step (the object STOP column, `ref_loss`, the predicted object) is `ReverieRolloutRecorder`.  The agents
-themselves and the simulator are out of scope."""
+themselves and the simulator are out of scope; their optimiser pair (optim) is here."""
 from .nav_graph import GoalSetEpisodes, NavEpisodes, NavGraphs, ReturnEpisodes
+from .optim import AgentOptimizers, build_agent_optimizers
 from .recorder import RolloutRecorder
 from .recorder_reverie import ReverieRolloutRecorder
 
-__all__ = ["GoalSetEpisodes", "NavEpisodes", "NavGraphs", "ReturnEpisodes", "ReverieRolloutRecorder", "RolloutRecorder"]
+__all__ = ["AgentOptimizers", "GoalSetEpisodes", "NavEpisodes", "NavGraphs", "ReturnEpisodes", "ReverieRolloutRecorder", "RolloutRecorder", "build_agent_optimizers"]

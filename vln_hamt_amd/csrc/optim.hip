@@ -2,6 +2,7 @@
 //   hamt_sumsq       global L2 norm of the gradient arena (torch clip_grad_norm_, main_r2r.py:271-273)
 //   hamt_adamw_flat  the reference's HF AdamW (optim/adamw.py:85-110) fused with the clip scaling, the
 //                    bf16 shadow refresh used by the MFMA GEMMs, and optimizer.zero_grad (main_r2r.py:280)
+//   hamt_optim_table torch.optim's AdamW / Adam / RMSprop / SGD, the finetune agents' optimisers (agent_cmt.py:62-77), same fusions
 // Traffic per parameter: read p,g,m,v (16 B) + write p,m,v (12 B) + g zero (4 B) + bf16 shadow (2 B) = 34 B.
 #include "common.h"
 
@@ -400,6 +401,126 @@ extern "C" int hamt_adamw_table_range(size_t first, size_t n, float* p, float* g
   hipLaunchKernelGGL((adamw_table_kernel<4>), dim3(nb), dim3(256), 0, as_stream(stream), n, p, g, m, v, (bf16_t*)p16, ends,
                      (const float4*)hyp, nparams, gnorm_sq, max_norm, beta1, beta2, eps, zero_grad, first / 4);
   HAMT_CHECK_LAUNCH("hamt_adamw_table");
+  return HAMT_OK;
+}
+// ---------------------------------------------------------------------------------------------------------------------------------
+// torch.optim's AdamW / Adam / RMSprop (momentum 0, not centered) / SGD (momentum 0) -- what the finetune agents run
+// (finetune_src/r2r/agent_cmt.py:62-77) -- over the same arenas, with adamw_table_kernel's sweep, loads in flight, store policies and
+// segment walk.  The rule is a template parameter: a rule's unused arenas are neither loaded nor stored (34 / 34 / 26 / 18 bytes per
+// element with the gradient slot zeroed), and the per-element code has no rule branch.
+// hyp[q] = {lr, lr / (1 - b1^t), weight_decay, active}, aux[q] = {1 / sqrt(1 - b2^t), 1 - lr * wd, 0, 0}; t is the parameter's own count.
+namespace {
+
+template <int RULE>
+__device__ __forceinline__ void optim_one(float& p, float g, float& m, float& v, float coef, const float4& h, const float4& a, float b1,
+                                          float b2, float eps) {
+  float gg = g * coef;
+  if constexpr (RULE == HAMT_OPT_ADAMW) p = p * a.y;               // param.mul_(1 - lr * wd), BEFORE the update   torch/optim/adamw.py
+  else gg = gg + h.z * p;                                          // grad = grad.add(param, alpha=wd)            (L2)
+  if constexpr (RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM) {
+    m = m * b1 + (1.0f - b1) * gg;                                 // exp_avg.lerp_(grad, 1 - b1)
+    v = v * b2 + (1.0f - b2) * gg * gg;                            // exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+    p = p - h.y * (m / (sqrtf(v) * a.x + eps));                    // denom = sqrt(v) / sqrt(1 - b2^t) + eps; p.addcdiv_(m, denom, -lr / (1 - b1^t))
+  } else if constexpr (RULE == HAMT_OPT_RMSPROP) {
+    v = v * b2 + (1.0f - b2) * gg * gg;                            // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    p = p - h.x * (gg / (sqrtf(v) + eps));                         // p.addcdiv_(grad, sqrt(square_avg) + eps, -lr)
+  } else {
+    p = p - h.x * gg;                                              // p.add_(grad, alpha=-lr)
+  }
+}
+
+template <int RULE, int U>
+__global__ __launch_bounds__(256) void optim_table_kernel(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16_t* __restrict__ p16, const int* __restrict__ ends,
+                                                          const float4* __restrict__ hyp, const float4* __restrict__ aux, int nparams,
+                                                          const float* __restrict__ gnorm_sq, float max_norm, float b1, float b2, float eps,
+                                                          int zero_grad) {
+  constexpr bool HAS_M = RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM, HAS_V = RULE != HAMT_OPT_SGD;
+  const float coef = clip_coef(gnorm_sq, max_norm);
+  const size_t n4 = n >> 2;
+  constexpr size_t CH = 256 * U;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  int pi = -1;
+  for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
+    const size_t hi = min(n4, lo + CH);
+    const long e0 = (long)lo * 4;
+    if (pi < 0) {   // binary search once: first parameter whose end is beyond this block's first element
+      int a = 0, b = nparams - 1;
+      while (a < b) { const int mid = (a + b) >> 1; if ((long)ends[mid] > e0) b = mid; else a = mid + 1; }
+      pi = a;
+    } else {
+      while (pi < nparams - 1 && (long)ends[pi] <= e0) ++pi;       // (the chunks of a block only move forward)
+    }
+    int q = pi;
+    for (size_t seg = lo; seg < hi; ++q) {
+      const size_t pend = q < nparams - 1 ? min(hi, (size_t)ends[q] >> 2) : hi;
+      const float4 h = hyp[q];
+      if (h.w != 0.f) {
+        const float4 ax = aux[q];
+        const bool zg = zero_grad && h.w == 1.f;
+        const size_t i = seg + threadIdx.x;
+        f4 P[U], G[U], M[U], V[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const size_t j = i + (size_t)u * 256;
+          if (j < pend) {
+            P[u] = ((const f4*)p)[j]; G[u] = ((const f4*)g)[j];
+            if constexpr (HAS_M) M[u] = ((const f4*)m)[j];
+            if constexpr (HAS_V) V[u] = ((const f4*)v)[j];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const size_t j = i + (size_t)u * 256;
+          if (j < pend) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              float pp = P[u][c], mm = HAS_M ? M[u][c] : 0.f, vv = HAS_V ? V[u][c] : 0.f;
+              optim_one<RULE>(pp, G[u][c], mm, vv, coef, h, ax, b1, b2, eps);
+              P[u][c] = pp;
+              if constexpr (HAS_M) M[u][c] = mm;
+              if constexpr (HAS_V) V[u][c] = vv;
+            }
+            __builtin_nontemporal_store(P[u], (f4*)p + j);
+            if constexpr (HAS_M) __builtin_nontemporal_store(M[u], (f4*)m + j);
+            if constexpr (HAS_V) __builtin_nontemporal_store(V[u], (f4*)v + j);
+            if (zg) __builtin_nontemporal_store((f4){0.f, 0.f, 0.f, 0.f}, (f4*)g + j);
+            if (p16) ((uint2*)p16)[j] = make_uint2(pack_bf2(P[u][0], P[u][1]), pack_bf2(P[u][2], P[u][3]));
+          }
+        }
+      }
+      seg = pend;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int hamt_optim_table(int rule, size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
+                                const float* aux, int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
+                                int zero_grad, void* stream) {
+  HAMT_CHECK_ARG(rule >= HAMT_OPT_ADAMW && rule <= HAMT_OPT_SGD, "hamt_optim_table: unknown rule");
+  const bool has_m = rule == HAMT_OPT_ADAMW || rule == HAMT_OPT_ADAM, has_v = rule != HAMT_OPT_SGD;
+  HAMT_CHECK_ARG(p && g && (m || !has_m) && (v || !has_v) && ends && hyp && aux && nparams > 0 && n % 4 == 0,
+                 "hamt_optim_table: bad argument (an arena the rule needs, ends, hyp or aux is NULL, or n is no multiple of 4)");
+  HAMT_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && (!has_m || ((uintptr_t)m % 16) == 0) &&
+                 (!has_v || ((uintptr_t)v % 16) == 0) && ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)aux % 16) == 0,
+                 "hamt_optim_table: arenas and tables must be 16-byte aligned");
+  if (n == 0) return HAMT_OK;
+  size_t b = (n / 4 + 1023) / 1024;              // adamw_table_kernel's geometry: 16-KiB chunks, at most 2 048 blocks sweeping together
+  const int nb = (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+  hipStream_t s = as_stream(stream);
+#define HAMT_OPTIM_LAUNCH(R)                                                                                                          \
+  hipLaunchKernelGGL((optim_table_kernel<R, 4>), dim3(nb), dim3(256), 0, s, n, p, g, m, v, (bf16_t*)p16, ends, (const float4*)hyp,     \
+                     (const float4*)aux, nparams, gnorm_sq, max_norm, beta1, beta2, eps, zero_grad)
+  switch (rule) {
+    case HAMT_OPT_ADAMW: HAMT_OPTIM_LAUNCH(HAMT_OPT_ADAMW); break;
+    case HAMT_OPT_ADAM: HAMT_OPTIM_LAUNCH(HAMT_OPT_ADAM); break;
+    case HAMT_OPT_RMSPROP: HAMT_OPTIM_LAUNCH(HAMT_OPT_RMSPROP); break;
+    default: HAMT_OPTIM_LAUNCH(HAMT_OPT_SGD); break;
+  }
+#undef HAMT_OPTIM_LAUNCH
+  HAMT_CHECK_LAUNCH("hamt_optim_table");
   return HAMT_OK;
 }
 extern "C" int hamt_clip_scale(size_t n, float* g, const float* gnorm_sq, float max_norm, void* stream) {

@@ -181,6 +181,19 @@ class AdamW(Optimizer):
         self._shard_stale = False
 
     # ---------------------------------------------------------------- arenas
+    owned_slice_update = True       # the update has a range form (hamt_adamw_table_range): attach() and parallel.ShardedGradSync use it
+
+    def _check_groups(self):
+        """the launch takes ONE set of the hyper-parameters that are not in the device table"""
+        b0 = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
+        for g in self.param_groups:
+            if (g["betas"], g["eps"]) != b0:
+                raise ValueError("AdamW: betas/eps must be the same in every group (they are in the reference)")
+
+    def _alloc_moments(self):
+        self._flat_m = torch.zeros_like(self._flat_p)
+        self._flat_v = torch.zeros_like(self._flat_p)
+
     def _build(self):
         ps, gidx = [], []
         for gi, group in enumerate(self.param_groups):
@@ -191,10 +204,7 @@ class AdamW(Optimizer):
             raise ValueError("AdamW: no parameters")
         if not ps[0].is_cuda:
             raise L.HamtError("AdamW: parameters must live on the GPU (no CPU fallback)")
-        b0 = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
-        for g in self.param_groups:
-            if (g["betas"], g["eps"]) != b0:
-                raise ValueError("AdamW: betas/eps must be the same in every group (they are in the reference)")
+        self._check_groups()
         dev = ps[0].device
         # Arena order: first the parameters the forward / backward only ever READ THROUGH THE bf16 SHADOW (the GEMM weights),
         # then everything that is read in fp32 (biases, LayerNorm, embedding tables, skinny / odd-width weights).  A sharded
@@ -218,8 +228,7 @@ class AdamW(Optimizer):
             self._flat_p[o:o + p.numel()].copy_(p.data.reshape(-1))
             p.data = self._flat_p[o:o + p.numel()].view(p.shape)
         self._flat_g = torch.zeros_like(self._flat_p)
-        self._flat_m = torch.zeros_like(self._flat_p)
-        self._flat_v = torch.zeros_like(self._flat_p)
+        self._alloc_moments()
         self._flat_p16 = torch.empty(n, dtype=torch.bfloat16, device=dev)
         L.check(L.load().hamt_cast_f32_bf16(n, _p(self._flat_p), _p(self._flat_p16), _stream()), "hamt_cast_f32_bf16")
         self._steps = np.zeros(len(ps), dtype=np.int64)
@@ -234,6 +243,7 @@ class AdamW(Optimizer):
         self._hyp_events = [None] * 4
         self._hyp_slot = 0
         self._hyp = torch.zeros(len(ps), 4, dtype=torch.float32, device=dev)
+        self._table_dev = self._hyp     # what upload_table fills (a subclass with a second table puts both in one block, _hyp first)
         self._gnorm = torch.zeros(1, dtype=torch.float32, device=dev)
         self._ws = torch.empty(L.workspace_bytes(L.WS_SUMSQ) // 4, dtype=torch.float32, device=dev)
         self._sync_shadow_views()
@@ -403,7 +413,7 @@ class AdamW(Optimizer):
             h[:] = 0.0
         else:
             h[:] = table
-        self._hyp.copy_(self._hyp_ring[k], non_blocking=True)
+        self._table_dev.copy_(self._hyp_ring[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self._hyp_events[k] = ev

@@ -61,6 +61,7 @@ class Ralamb(AdamW):
     """The reference's Ralamb (ralamb.py) on the arenas: RangerLars without the Lookahead wrapper."""
 
     _lookahead = False
+    owned_slice_update = False      # every parameter's trust ratio needs its whole norm
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         if lr < 0.0:

@@ -361,16 +361,16 @@ def shardable(optimizer, world: int) -> bool:
 
 
 def per_tensor_update(optimizer) -> bool:
-    """Does the optimizer's update need every parameter's whole norm (optim.rangerlars: the trust ratio)?  The sharded exchange
-    updates owned slices that cut through parameters: such an optimizer takes the all-reduce exchange."""
-    from .optim.rangerlars import Ralamb
-    return isinstance(optimizer, Ralamb)
+    """Has the optimizer NO owned-slice update?  The sharded exchange updates arena ranges that cut through parameters: an update
+    that needs every parameter's whole norm (optim.rangerlars: the trust ratio) or has no range form of its kernel
+    (optim.torch_rules) says so in its class (`owned_slice_update = False`) and takes the all-reduce exchange."""
+    return not getattr(optimizer, "owned_slice_update", True)
 
 
 def make_grad_sync(optimizer, prec: str = "bf16", n_groups: int = 4, wire: str | None = None, sharded: bool | None = None):
     """The gradient exchange for this process group: ShardedGradSync (reduce-scatter, owned-slice AdamW, all-gather) in bf16 mode
     when the arenas split evenly over the ranks, else OverlappedGradSync (all-reduce, full AdamW on every rank).  A RangerLars
-    always gets OverlappedGradSync (per_tensor_update)."""
+    and the torch-rule optimizers of the finetune agents always get OverlappedGradSync (per_tensor_update)."""
     wire = wire or default_wire(prec)
     world = dist.get_world_size() if dist.is_initialized() else 1
     if sharded is None:
@@ -406,8 +406,9 @@ class ShardedGradSync(OverlappedGradSync):
 
     def __init__(self, optimizer, n_groups: int = 4, wire: str = "fp32"):
         if per_tensor_update(optimizer):
-            raise ValueError(f"ShardedGradSync: {type(optimizer).__name__} needs each parameter's whole norm for its trust ratio, the owned "
-                             "slices cut through parameters; use the all-reduce exchange (OverlappedGradSync, which make_grad_sync picks)")
+            raise ValueError(f"ShardedGradSync: {type(optimizer).__name__} has no update over owned slices that cut through parameters (a "
+                             "trust ratio needs each parameter's whole norm; the torch rules have no range kernel); use the all-reduce "
+                             "exchange (OverlappedGradSync, which make_grad_sync picks)")
         super().__init__(optimizer, n_groups, wire)
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
