@@ -1354,6 +1354,43 @@ def test_wire_unpack_sumsq():
     assert abs(float(out) - want) <= 1e-5 * want, (float(out), want)
 
 
+def sumsq_table_case(nparams):
+    """a table of nparams parameters of 4 .. 7 996 elements with every kind of flag, and an arena range [first, first + n) that starts
+    inside the first parameter and ends inside the last: sizes, flags, ends and hyp (device), first, n"""
+    rs = np.random.RandomState(nparams)
+    sizes = (rs.randint(1, 2000, size=nparams) * 4).tolist()
+    flags = rs.choice([0.0, 1.0, 2.0, 3.0], size=nparams, p=[0.3, 0.1, 0.1, 0.5]).tolist()
+    ends = torch.tensor(np.cumsum(sizes), dtype=torch.int32, device=DEV)
+    hyp = torch.zeros(nparams, 4, device=DEV)
+    hyp[:, 3] = torch.tensor(flags)
+    first = (sizes[0] // 8) * 4
+    n = sum(sizes) - first - (sizes[-1] // 8) * 4
+    return sizes, flags, ends, hyp, first, n
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+def test_wire_unpack_sumsq_beyond_one_sweep(accumulate):
+    """hamt_wire_unpack_sumsq over a range of more than one sweep of its 1 024-block grid (16-KiB chunks): the first blocks take a second
+    chunk, and their segment walk moves forward from the parameter of the first one.  1 500 parameters with all four flags, the range
+    starts and ends inside parameters: g == float(y) inside the range bit for bit, NaN outside, the sum against fp64."""
+    from vln_hamt_amd import _lib as L
+    ops = _ops()
+    sizes, flags, ends, hyp, first, n = sumsq_table_case(1500)
+    n_all = sum(sizes)
+    assert n > 1024 * 4096 and 0 < first < sizes[0] and n_all - sizes[-1] < first + n < n_all
+    y = rnd(n_all, seed=4).to(torch.bfloat16).to(DEV)
+    g = torch.full((n_all,), float("nan"), device=DEV)
+    out = torch.full((1,), 3.0, device=DEV)
+    ws = torch.empty(1024, device=DEV)
+    L.check(L.load().hamt_wire_unpack_sumsq(first, n, ops._p(y[first:first + n]), ops._p(g[first:first + n]), ops._p(ends), ops._p(hyp), len(sizes),
+                                            ops._p(out), accumulate, ops._p(ws), ops._stream()), "hamt_wire_unpack_sumsq")
+    torch.cuda.synchronize()
+    assert torch.equal(g[first:first + n], y[first:first + n].float()) and bool(torch.isnan(g[:first]).all()) and bool(torch.isnan(g[first + n:]).all())
+    act = torch.cat([torch.full((sz,), f in (1.0, 2.0)) for sz, f in zip(sizes, flags)]).to(DEV)
+    want = 3.0 * accumulate + float((y.double() ** 2)[first:first + n][act[first:first + n]].sum())
+    assert abs(float(out) - want) <= 1e-5 * want, (float(out), want)
+
+
 @pytest.mark.parametrize("sparse", [0, 2])
 @pytest.mark.parametrize("nparams", [5, 300, 1500])
 def test_sumsq_table_active_only(sparse, nparams):
@@ -1362,19 +1399,12 @@ def test_sumsq_table_active_only(sparse, nparams):
     elements spread evenly over the blocks: the GEMM-weight region of a step) against fp64."""
     from vln_hamt_amd import _lib as L
     ops = _ops()
-    rs = np.random.RandomState(nparams)
-    sizes = (rs.randint(1, 2000, size=nparams) * 4).tolist()
-    flags = rs.choice([0.0, 1.0, 2.0, 3.0], size=nparams, p=[0.3, 0.1, 0.1, 0.5]).tolist()
-    ends = torch.tensor(np.cumsum(sizes), dtype=torch.int32, device=DEV)
-    hyp = torch.zeros(nparams, 4, device=DEV)
-    hyp[:, 3] = torch.tensor(flags)
+    sizes, flags, ends, hyp, first, n = sumsq_table_case(nparams)
     n_all = sum(sizes)
     g = rnd(n_all, seed=5).to(DEV)
     act = torch.cat([torch.full((sz,), f in (1.0, 2.0)) for sz, f in zip(sizes, flags)]).to(DEV)
     dead = torch.cat([torch.full((sz,), f == 0.0) for sz, f in zip(sizes, flags)]).to(DEV)
     g[dead] = float("nan")
-    first = (sizes[0] // 8) * 4
-    n = n_all - first - (sizes[-1] // 8) * 4
     out = torch.full((1,), 2.0, device=DEV)
     ws = torch.empty(1024, device=DEV)
     L.check(L.load().hamt_sumsq_table(first, n, ops._p(g[first:first + n]), ops._p(ends), ops._p(hyp), nparams, ops._p(out), 1 | sparse,

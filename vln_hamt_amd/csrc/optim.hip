@@ -8,6 +8,15 @@
 
 namespace {
 
+// The sum of `s` over a block of 256 threads, in a fixed order: the butterfly inside each wave, then (w0 + w1) + (w2 + w3).  Every thread
+// gets it; one call per kernel (one LDS buffer, no barrier behind the read).
+__device__ __forceinline__ float block_sum(float s) {
+  __shared__ float red[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(size_t n, const float* __restrict__ g, float* __restrict__ ws) {
   float s = 0.f;
   const size_t n4 = n >> 2;
@@ -16,30 +25,32 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(size_t n, const floa
     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const float v = g[n4 * 4 + threadIdx.x]; s += v * v; }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum(s);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ __launch_bounds__(256) void sumsq_final_kernel(int nb, const float* __restrict__ ws, float* __restrict__ out, int accumulate) {
   float s = 0.f;
   for (int i = threadIdx.x; i < nb; i += 256) s += ws[i];
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) { const float t = (red[0] + red[1]) + (red[2] + red[3]); *out = accumulate ? *out + t : t; }
+  s = block_sum(s);
+  if (threadIdx.x == 0) *out = accumulate ? *out + s : s;
 }
 __device__ __forceinline__ float clip_coef(const float* gnorm_sq, float max_norm) {
   if (!gnorm_sq || max_norm <= 0.f) return 1.0f;
   return fminf(1.0f, max_norm / (sqrtf(*gnorm_sq) + 1e-6f));
 }
+// avg * beta + w * x, the step of an exponential average, with the FMA spelled out.  As `avg * beta + w * x` the compiler fuses whichever
+// product the operand order of the add offers first, and that order is canonicalised anew in every function the expression is inlined
+// through: moving the sweep body into a shared function changed the rounding of v.  So the choice is made here.  FUSE_DECAY false:
+// avg * beta is rounded on its own, as the references' mul_ does; true: w * x is.
+template <bool FUSE_DECAY>
+__device__ __forceinline__ float ema(float avg, float beta, float w, float x) {
+  return FUSE_DECAY ? fmaf(avg, beta, w * x) : fmaf(w, x, avg * beta);
+}
 __device__ __forceinline__ void adamw_one(float& p, float& g, float& m, float& v, float coef, float lr, float step, float b1,
                                           float b2, float eps, float wd) {
   const float gg = g * coef;
-  m = m * b1 + (1.0f - b1) * gg;                    // exp_avg.mul_(b1).add_(grad, alpha=1-b1)           adamw.py:89
-  v = v * b2 + (1.0f - b2) * gg * gg;               // exp_avg_sq.mul_(b2).addcmul_(grad, grad, 1-b2)    adamw.py:90
+  m = ema<false>(m, b1, 1.0f - b1, gg);             // exp_avg.mul_(b1).add_(grad, alpha=1-b1)           adamw.py:89
+  v = ema<false>(v, b2, gg, (1.0f - b2) * gg);      // exp_avg_sq.mul_(b2).addcmul_(grad, grad, 1-b2)    adamw.py:90
   p = p - step * (m / (sqrtf(v) + eps));            // denom = sqrt(v)+eps; p.addcdiv_(m, denom, -step)  adamw.py:91-99
   if (wd > 0.f) p = p - lr * wd * p;                // decoupled decay AFTER the update                   adamw.py:109-110
 }
@@ -81,49 +92,112 @@ __global__ __launch_bounds__(256) void adamw_kernel(size_t n, float* __restrict_
 // hyper-parameters of its one or two parameters in registers): that form's time moved 945 -> 1 140 us from PROCESS to process (and so from
 // box to box: VERDICT r4 weak 11) while a plain 1-GiB copy held 5.35 - 5.46 TB/s in every one of them -- ten thousand concurrently streamed
 // regions depend on how the driver happened to back the arenas (translation reach), a narrow moving window does not: 968 - 983 us in every
-// process (tools/r5_adamw2.sh; 1 024 blocks the same, 4 096 blocks 1 016 - 1 024 us).
-template <int U>
-__global__ __launch_bounds__(256) void adamw_table_kernel(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                                float* __restrict__ v, bf16_t* __restrict__ p16, const int* __restrict__ ends,
-                                                                const float4* __restrict__ hyp, int nparams, const float* __restrict__ gnorm_sq,
-                                                                float max_norm, float b1, float b2, float eps, int zero_grad, size_t first4) {
-  const float coef = clip_coef(gnorm_sq, max_norm);
-  const size_t n4 = n >> 2;
-  constexpr size_t CH = 256 * U;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  int pi = -1;
-  for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
-    const size_t hi = min(n4, lo + CH);
+// process (tools/r5_adamw2.sh; 1 024 blocks the same, 4 096 blocks 1 016 - 1 024 us).  table_sweep below is that kernel body.
+//
+// The segment walk of the table kernels.  A block's chunk [lo, hi) (float4 offsets inside the launch's range, which starts at float4
+// `first4` of the arena and may start and end inside parameters) is cut into the segments of the parameters it touches:
+//     int q = walk.seek(lo);
+//     for (size_t seg = lo; seg < hi; ++q) { const size_t pend = walk.end(q, hi);  ... [seg, pend) is of parameter q ...  seg = pend; }
+// A chunk may hold dozens of parameters; the last parameter owns the padding behind it.
+struct SegWalk {
+  const int* __restrict__ ends;
+  int nparams;
+  size_t first4;
+  int pi;
+  __device__ __forceinline__ SegWalk(const int* __restrict__ ends_, int nparams_, size_t first4_) : ends(ends_), nparams(nparams_), first4(first4_), pi(-1) {}
+  // the parameter that holds the chunk's first element: the first one whose end is beyond it
+  __device__ __forceinline__ int seek(size_t lo) {
     const long e0 = (long)(lo + first4) * 4;
-    if (pi < 0) {   // binary search once: first parameter whose end is beyond this block's first element
+    if (pi < 0) {   // binary search once
       int a = 0, b = nparams - 1;
       while (a < b) { const int mid = (a + b) >> 1; if ((long)ends[mid] > e0) b = mid; else a = mid + 1; }
       pi = a;
     } else {
       while (pi < nparams - 1 && (long)ends[pi] <= e0) ++pi;       // (the chunks of a block only move forward)
     }
-    int q = pi;
+    return pi;
+  }
+  __device__ __forceinline__ size_t end(int q, size_t hi) const { return q < nparams - 1 ? min(hi, ((size_t)ends[q] >> 2) - first4) : hi; }
+};
+// The per-element rules of the sweep: the reference's HF AdamW (adamw_one; an internal rule, not one of hamt_opt_rule) and torch.optim's
+// AdamW / Adam / RMSprop (momentum 0, not centered) / SGD (momentum 0) -- what the finetune agents run (finetune_src/r2r/agent_cmt.py:62-77).
+// The rule is a template parameter: a rule's unused arenas are neither loaded nor stored (34 / 34 / 26 / 18 bytes per element with the
+// gradient slot zeroed), and the per-element code has no rule branch.
+// HF AdamW: hyp[q] = {lr, step_size, weight_decay, active}, no aux.
+// torch's:  hyp[q] = {lr, lr / (1 - b1^t), weight_decay, active}, aux[q] = {1 / sqrt(1 - b2^t), 1 - lr * wd, 0, 0}; t is the parameter's own count.
+constexpr int RULE_HF_ADAMW = -1;
+static_assert(HAMT_OPT_ADAMW >= 0, "RULE_HF_ADAMW must not collide with hamt_opt_rule");
+template <int RULE>
+__device__ __forceinline__ void optim_one(float& p, float g, float& m, float& v, float coef, const float4& h, const float4& a, float b1,
+                                          float b2, float eps) {
+  if constexpr (RULE == RULE_HF_ADAMW) {
+    adamw_one(p, g, m, v, coef, h.x, h.y, b1, b2, eps, h.z);
+    return;
+  }
+  constexpr bool L2 = RULE != HAMT_OPT_ADAMW;                      // (the rules with the L2 term fuse the decay product of m and v, AdamW the
+  float gg = g * coef;                                             //  other one: how each kernel was first compiled, kept bit for bit -- see ema)
+  if constexpr (RULE == HAMT_OPT_ADAMW) p = p * a.y;               // param.mul_(1 - lr * wd), BEFORE the update   torch/optim/adamw.py
+  else gg = gg + h.z * p;                                          // grad = grad.add(param, alpha=wd)            (L2)
+  if constexpr (RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM) {
+    m = ema<L2>(m, b1, 1.0f - b1, gg);                             // exp_avg.lerp_(grad, 1 - b1)
+    v = ema<L2>(v, b2, gg, (1.0f - b2) * gg);                      // exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
+    p = p - h.y * (m / (sqrtf(v) * a.x + eps));                    // denom = sqrt(v) / sqrt(1 - b2^t) + eps; p.addcdiv_(m, denom, -lr / (1 - b1^t))
+  } else if constexpr (RULE == HAMT_OPT_RMSPROP) {
+    v = ema<L2>(v, b2, gg, (1.0f - b2) * gg);                      // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    p = p - h.x * (gg / (sqrtf(v) + eps));                         // p.addcdiv_(grad, sqrt(square_avg) + eps, -lr)
+  } else {
+    p = p - h.x * gg;                                              // p.add_(grad, alpha=-lr)
+  }
+}
+// The sweep body of adamw_table_kernel and optim_table_kernel (see the comment above): U float4 of each arena the rule owns in flight
+// per thread, p / m / v and the zeroed gradient slot stored non-temporally, the bf16 shadow at the default policy.
+template <int RULE, int U>
+__device__ __forceinline__ void table_sweep(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            bf16_t* __restrict__ p16, const int* __restrict__ ends, const float4* __restrict__ hyp,
+                                            const float4* __restrict__ aux, int nparams, const float* __restrict__ gnorm_sq, float max_norm,
+                                            float b1, float b2, float eps, int zero_grad, size_t first4) {
+  constexpr bool HF = RULE == RULE_HF_ADAMW;
+  constexpr bool HAS_M = HF || RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM, HAS_V = RULE != HAMT_OPT_SGD;
+  const float coef = clip_coef(gnorm_sq, max_norm);
+  const size_t n4 = n >> 2;
+  constexpr size_t CH = 256 * U;
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  SegWalk walk(ends, nparams, first4);
+  for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
+    const size_t hi = min(n4, lo + CH);
+    int q = walk.seek(lo);
     for (size_t seg = lo; seg < hi; ++q) {
-      const size_t pend = q < nparams - 1 ? min(hi, ((size_t)ends[q] >> 2) - first4) : hi;
+      const size_t pend = walk.end(q, hi);
       const float4 h = hyp[q];
       if (h.w != 0.f) {
+        const float4 ax = HF ? make_float4(0.f, 0.f, 0.f, 0.f) : aux[q];
         const bool zg = zero_grad && h.w == 1.f;
         const size_t i = seg + threadIdx.x;
         f4 P[U], G[U], M[U], V[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const size_t j = i + (size_t)u * 256;
-          if (j < pend) { P[u] = ((const f4*)p)[j]; G[u] = ((const f4*)g)[j]; M[u] = ((const f4*)m)[j]; V[u] = ((const f4*)v)[j]; }
+          if (j < pend) {
+            P[u] = ((const f4*)p)[j]; G[u] = ((const f4*)g)[j];
+            if constexpr (HAS_M) M[u] = ((const f4*)m)[j];
+            if constexpr (HAS_V) V[u] = ((const f4*)v)[j];
+          }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const size_t j = i + (size_t)u * 256;
           if (j < pend) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { float pp = P[u][c], gg = G[u][c], mm = M[u][c], vv = V[u][c]; adamw_one(pp, gg, mm, vv, coef, h.x, h.y, b1, b2, eps, h.z); P[u][c] = pp; M[u][c] = mm; V[u][c] = vv; }
+            for (int c = 0; c < 4; ++c) {
+              float pp = P[u][c], mm = HAS_M ? M[u][c] : 0.f, vv = HAS_V ? V[u][c] : 0.f;
+              optim_one<RULE>(pp, G[u][c], mm, vv, coef, h, ax, b1, b2, eps);
+              P[u][c] = pp;
+              if constexpr (HAS_M) M[u][c] = mm;
+              if constexpr (HAS_V) V[u][c] = vv;
+            }
             __builtin_nontemporal_store(P[u], (f4*)p + j);
-            __builtin_nontemporal_store(M[u], (f4*)m + j);
-            __builtin_nontemporal_store(V[u], (f4*)v + j);
+            if constexpr (HAS_M) __builtin_nontemporal_store(M[u], (f4*)m + j);
+            if constexpr (HAS_V) __builtin_nontemporal_store(V[u], (f4*)v + j);
             if (zg) __builtin_nontemporal_store((f4){0.f, 0.f, 0.f, 0.f}, (f4*)g + j);
             if (p16) ((uint2*)p16)[j] = make_uint2(pack_bf2(P[u][0], P[u][1]), pack_bf2(P[u][2], P[u][3]));
           }
@@ -133,31 +207,37 @@ __global__ __launch_bounds__(256) void adamw_table_kernel(size_t n, float* __res
     }
   }
 }
-// sum(g^2) over the ACTIVE parameters of an arena range (same segment walk as adamw_table_kernel): slots of inactive
-// parameters are not read (they may hold a stale gradient, see active == 2 above).  One partial per block, summed in block
-// order by sumsq_final_kernel: deterministic.
+template <int U>
+__global__ __launch_bounds__(256) void adamw_table_kernel(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16_t* __restrict__ p16, const int* __restrict__ ends,
+                                                          const float4* __restrict__ hyp, int nparams, const float* __restrict__ gnorm_sq,
+                                                          float max_norm, float b1, float b2, float eps, int zero_grad, size_t first4) {
+  table_sweep<RULE_HF_ADAMW, U>(n, p, g, m, v, p16, ends, hyp, nullptr, nparams, gnorm_sq, max_norm, b1, b2, eps, zero_grad, first4);
+}
+template <int RULE, int U>
+__global__ __launch_bounds__(256) void optim_table_kernel(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16_t* __restrict__ p16, const int* __restrict__ ends,
+                                                          const float4* __restrict__ hyp, const float4* __restrict__ aux, int nparams,
+                                                          const float* __restrict__ gnorm_sq, float max_norm, float b1, float b2, float eps,
+                                                          int zero_grad) {
+  table_sweep<RULE, U>(n, p, g, m, v, p16, ends, hyp, aux, nparams, gnorm_sq, max_norm, b1, b2, eps, zero_grad, 0);
+}
+// sum(g^2) over the ACTIVE parameters of an arena range: slots of inactive parameters are not read (they may hold a stale gradient,
+// see active == 2 above).  One partial per block, summed in block order by sumsq_final_kernel: deterministic.
 __global__ __launch_bounds__(256) void sumsq_table_partial_kernel(size_t n, const float* __restrict__ g, const int* __restrict__ ends,
                                                                   const float4* __restrict__ hyp, int nparams, size_t first4,
                                                                   float* __restrict__ ws) {
-  // (the blocks sweep the range together, 16-KiB chunks b, b + gridDim, ...: see adamw_table_kernel; a block's partial is the sum over ITS
+  // (the blocks sweep the range together, 16-KiB chunks b, b + gridDim, ...: the pattern of table_sweep; a block's partial is the sum over ITS
   // chunks in order, the partials are summed in block order: a fixed partition for a given grid, deterministic)
   const size_t n4 = n >> 2;
   constexpr size_t CH = 256 * 4;
   float s = 0.f;
-  int pi = -1;
+  SegWalk walk(ends, nparams, first4);
   for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
     const size_t hi = min(n4, lo + CH);
-    const long e0 = (long)(lo + first4) * 4;
-    if (pi < 0) {
-      int a = 0, b = nparams - 1;
-      while (a < b) { const int mid = (a + b) >> 1; if ((long)ends[mid] > e0) b = mid; else a = mid + 1; }
-      pi = a;
-    } else {
-      while (pi < nparams - 1 && (long)ends[pi] <= e0) ++pi;
-    }
-    int q = pi;
+    int q = walk.seek(lo);
     for (size_t seg = lo; seg < hi; ++q) {
-      const size_t pend = q < nparams - 1 ? min(hi, ((size_t)ends[q] >> 2) - first4) : hi;
+      const size_t pend = walk.end(q, hi);
       const float act = hyp[q].w;
       if (act != 0.f && act != 3.f) {      // 3: accounted for by the weight-gradient tiles (hamt_wgrad_desc.ss)
         const size_t i = seg + threadIdx.x;
@@ -170,11 +250,8 @@ __global__ __launch_bounds__(256) void sumsq_table_partial_kernel(size_t n, cons
       seg = pend;
     }
   }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum(s);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 // The same sum with the ACTIVE elements spread evenly over the blocks.  When most of a range is skipped (the GEMM-weight region once the
 // weight-gradient tiles carry their own sums: what is left are the few weights written twice in a pass, ~6 % of the range in a handful
@@ -238,36 +315,24 @@ __global__ __launch_bounds__(256) void sumsq_table_balanced_kernel(size_t n, con
       }
     }
   }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  if (t == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum(s);
+  if (t == 0) ws[blockIdx.x] = s;
 }
-// The same walk fused with the widening of a reduce-scattered bf16 gradient chunk: g[i] = float(y16[i]) for EVERY element of the
+// That sum fused with the widening of a reduce-scattered bf16 gradient chunk: g[i] = float(y16[i]) for EVERY element of the
 // chunk, sum of squares over the active parameters only -- one pass instead of hamt_wire_unpack_bf16 followed by hamt_sumsq_table
 // (the exchange of a data-parallel step runs this once per arena range, behind the range's reduce-scatter).
 __global__ __launch_bounds__(256) void unpack_sumsq_partial_kernel(size_t n, const bf16_t* __restrict__ y, float* __restrict__ g,
                                                                    const int* __restrict__ ends, const float4* __restrict__ hyp, int nparams,
                                                                    size_t first4, float* __restrict__ ws) {
-  // (16-KiB chunks b, b + gridDim, ...: the blocks sweep the range together, see adamw_table_kernel)
   const size_t n4 = n >> 2;
   constexpr size_t CH = 256 * 4;
   float s = 0.f;
-  int pi = -1;
+  SegWalk walk(ends, nparams, first4);
   for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
     const size_t hi = min(n4, lo + CH);
-    const long e0 = (long)(lo + first4) * 4;
-    if (pi < 0) {
-      int a = 0, b = nparams - 1;
-      while (a < b) { const int mid = (a + b) >> 1; if ((long)ends[mid] > e0) b = mid; else a = mid + 1; }
-      pi = a;
-    } else {
-      while (pi < nparams - 1 && (long)ends[pi] <= e0) ++pi;
-    }
-    int k = pi;
+    int k = walk.seek(lo);
     for (size_t seg = lo; seg < hi; ++k) {
-      const size_t pend = k < nparams - 1 ? min(hi, ((size_t)ends[k] >> 2) - first4) : hi;
+      const size_t pend = walk.end(k, hi);
       const bool act = hyp[k].w != 0.f && hyp[k].w != 3.f;
       const size_t i = seg + threadIdx.x;
       uint2 u[4];
@@ -284,11 +349,8 @@ __global__ __launch_bounds__(256) void unpack_sumsq_partial_kernel(size_t n, con
       seg = pend;
     }
   }
-  __shared__ float red[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) ws[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum(s);
+  if (threadIdx.x == 0) ws[blockIdx.x] = s;
 }
 __global__ void clip_scale_kernel(size_t n, float* __restrict__ g, const float* __restrict__ gnorm_sq, float max_norm) {
   const float coef = clip_coef(gnorm_sq, max_norm);
@@ -296,6 +358,12 @@ __global__ void clip_scale_kernel(size_t n, float* __restrict__ g, const float* 
 }
 
 }  // namespace
+
+// blocks for a range of n floats in 16-KiB chunks (256 threads x 4 float4), 1 .. cap: beyond cap the grid sweeps the chunks together
+static inline int chunk_grid(size_t n, size_t cap) {
+  const size_t b = (n / 4 + 1023) / 1024;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 extern "C" int hamt_sumsq(size_t n, const float* g, float* out, int accumulate, float* ws, void* stream) {
   HAMT_CHECK_ARG(g && out && ws && ((uintptr_t)g % 16) == 0, "hamt_sumsq: bad argument (ws needs 1024 floats, g 16-byte aligned)");
@@ -312,8 +380,7 @@ extern "C" int hamt_sumsq_table(size_t first, size_t n, const float* g, const in
   HAMT_CHECK_ARG(g && out && ws && ends && hyp && nparams > 0 && n % 4 == 0 && first % 4 == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)hyp % 16) == 0,
                  "hamt_sumsq_table: bad argument (ws needs 1024 floats, g / hyp 16-byte aligned, first and n multiples of 4)");
   hipStream_t s = as_stream(stream);
-  size_t b = (n / 4 + 1023) / 1024;
-  int nb = (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+  int nb = chunk_grid(n, 1024);
   static const bool balanced = getenv("HAMT_SUMSQ_UNBALANCED") == nullptr;
   const bool sparse = (accumulate & HAMT_SUMSQ_SPARSE) != 0;
   accumulate &= 1;
@@ -332,8 +399,7 @@ extern "C" int hamt_wire_unpack_sumsq(size_t first, size_t n, const void* y16, f
                  ((uintptr_t)y16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0,
                  "hamt_wire_unpack_sumsq: bad argument (ws needs 1024 floats, g / hyp 16-byte and y16 8-byte aligned, first and n multiples of 4)");
   hipStream_t s = as_stream(stream);
-  size_t b = (n / 4 + 1023) / 1024;
-  int nb = (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+  const int nb = chunk_grid(n, 1024);
   hipLaunchKernelGGL(unpack_sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, n, (const bf16_t*)y16, g, ends, (const float4*)hyp, nparams, first / 4, ws);
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, nb, ws, out, accumulate);
   HAMT_CHECK_LAUNCH("hamt_wire_unpack_sumsq");
@@ -383,119 +449,22 @@ extern "C" int hamt_adamw_flat(size_t n, float* p, float* g, float* m, float* v,
 }
 extern "C" int hamt_adamw_table_range(size_t first, size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
                                       int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
-                                      int zero_grad, void* stream);
-extern "C" int hamt_adamw_table(size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
-                                int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
-                                int zero_grad, void* stream) {
-  return hamt_adamw_table_range(0, n, p, g, m, v, p16, ends, hyp, nparams, gnorm_sq, max_norm, beta1, beta2, eps, zero_grad, stream);
-}
-extern "C" int hamt_adamw_table_range(size_t first, size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
-                                      int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
                                       int zero_grad, void* stream) {
   HAMT_CHECK_ARG(p && g && m && v && ends && hyp && nparams > 0 && n % 4 == 0 && first % 4 == 0, "hamt_adamw_table: bad argument");
   HAMT_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
                  ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0, "hamt_adamw_table: arenas must be 16-byte aligned");
   if (n == 0) return HAMT_OK;
-  size_t b = (n / 4 + 1023) / 1024;              // 16-KiB chunks of 256 x 4 float4; the grid sweeps them together (see the kernel)
-  int nb = (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+  const int nb = chunk_grid(n, 2048);
   hipLaunchKernelGGL((adamw_table_kernel<4>), dim3(nb), dim3(256), 0, as_stream(stream), n, p, g, m, v, (bf16_t*)p16, ends,
                      (const float4*)hyp, nparams, gnorm_sq, max_norm, beta1, beta2, eps, zero_grad, first / 4);
   HAMT_CHECK_LAUNCH("hamt_adamw_table");
   return HAMT_OK;
 }
-// ---------------------------------------------------------------------------------------------------------------------------------
-// torch.optim's AdamW / Adam / RMSprop (momentum 0, not centered) / SGD (momentum 0) -- what the finetune agents run
-// (finetune_src/r2r/agent_cmt.py:62-77) -- over the same arenas, with adamw_table_kernel's sweep, loads in flight, store policies and
-// segment walk.  The rule is a template parameter: a rule's unused arenas are neither loaded nor stored (34 / 34 / 26 / 18 bytes per
-// element with the gradient slot zeroed), and the per-element code has no rule branch.
-// hyp[q] = {lr, lr / (1 - b1^t), weight_decay, active}, aux[q] = {1 / sqrt(1 - b2^t), 1 - lr * wd, 0, 0}; t is the parameter's own count.
-namespace {
-
-template <int RULE>
-__device__ __forceinline__ void optim_one(float& p, float g, float& m, float& v, float coef, const float4& h, const float4& a, float b1,
-                                          float b2, float eps) {
-  float gg = g * coef;
-  if constexpr (RULE == HAMT_OPT_ADAMW) p = p * a.y;               // param.mul_(1 - lr * wd), BEFORE the update   torch/optim/adamw.py
-  else gg = gg + h.z * p;                                          // grad = grad.add(param, alpha=wd)            (L2)
-  if constexpr (RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM) {
-    m = m * b1 + (1.0f - b1) * gg;                                 // exp_avg.lerp_(grad, 1 - b1)
-    v = v * b2 + (1.0f - b2) * gg * gg;                            // exp_avg_sq.mul_(b2).addcmul_(grad, grad, value=1 - b2)
-    p = p - h.y * (m / (sqrtf(v) * a.x + eps));                    // denom = sqrt(v) / sqrt(1 - b2^t) + eps; p.addcdiv_(m, denom, -lr / (1 - b1^t))
-  } else if constexpr (RULE == HAMT_OPT_RMSPROP) {
-    v = v * b2 + (1.0f - b2) * gg * gg;                            // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
-    p = p - h.x * (gg / (sqrtf(v) + eps));                         // p.addcdiv_(grad, sqrt(square_avg) + eps, -lr)
-  } else {
-    p = p - h.x * gg;                                              // p.add_(grad, alpha=-lr)
-  }
+extern "C" int hamt_adamw_table(size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
+                                int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
+                                int zero_grad, void* stream) {
+  return hamt_adamw_table_range(0, n, p, g, m, v, p16, ends, hyp, nparams, gnorm_sq, max_norm, beta1, beta2, eps, zero_grad, stream);
 }
-
-template <int RULE, int U>
-__global__ __launch_bounds__(256) void optim_table_kernel(size_t n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                          float* __restrict__ v, bf16_t* __restrict__ p16, const int* __restrict__ ends,
-                                                          const float4* __restrict__ hyp, const float4* __restrict__ aux, int nparams,
-                                                          const float* __restrict__ gnorm_sq, float max_norm, float b1, float b2, float eps,
-                                                          int zero_grad) {
-  constexpr bool HAS_M = RULE == HAMT_OPT_ADAMW || RULE == HAMT_OPT_ADAM, HAS_V = RULE != HAMT_OPT_SGD;
-  const float coef = clip_coef(gnorm_sq, max_norm);
-  const size_t n4 = n >> 2;
-  constexpr size_t CH = 256 * U;
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  int pi = -1;
-  for (size_t lo = (size_t)blockIdx.x * CH; lo < n4; lo += (size_t)gridDim.x * CH) {
-    const size_t hi = min(n4, lo + CH);
-    const long e0 = (long)lo * 4;
-    if (pi < 0) {   // binary search once: first parameter whose end is beyond this block's first element
-      int a = 0, b = nparams - 1;
-      while (a < b) { const int mid = (a + b) >> 1; if ((long)ends[mid] > e0) b = mid; else a = mid + 1; }
-      pi = a;
-    } else {
-      while (pi < nparams - 1 && (long)ends[pi] <= e0) ++pi;       // (the chunks of a block only move forward)
-    }
-    int q = pi;
-    for (size_t seg = lo; seg < hi; ++q) {
-      const size_t pend = q < nparams - 1 ? min(hi, (size_t)ends[q] >> 2) : hi;
-      const float4 h = hyp[q];
-      if (h.w != 0.f) {
-        const float4 ax = aux[q];
-        const bool zg = zero_grad && h.w == 1.f;
-        const size_t i = seg + threadIdx.x;
-        f4 P[U], G[U], M[U], V[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const size_t j = i + (size_t)u * 256;
-          if (j < pend) {
-            P[u] = ((const f4*)p)[j]; G[u] = ((const f4*)g)[j];
-            if constexpr (HAS_M) M[u] = ((const f4*)m)[j];
-            if constexpr (HAS_V) V[u] = ((const f4*)v)[j];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const size_t j = i + (size_t)u * 256;
-          if (j < pend) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              float pp = P[u][c], mm = HAS_M ? M[u][c] : 0.f, vv = HAS_V ? V[u][c] : 0.f;
-              optim_one<RULE>(pp, G[u][c], mm, vv, coef, h, ax, b1, b2, eps);
-              P[u][c] = pp;
-              if constexpr (HAS_M) M[u][c] = mm;
-              if constexpr (HAS_V) V[u][c] = vv;
-            }
-            __builtin_nontemporal_store(P[u], (f4*)p + j);
-            if constexpr (HAS_M) __builtin_nontemporal_store(M[u], (f4*)m + j);
-            if constexpr (HAS_V) __builtin_nontemporal_store(V[u], (f4*)v + j);
-            if (zg) __builtin_nontemporal_store((f4){0.f, 0.f, 0.f, 0.f}, (f4*)g + j);
-            if (p16) ((uint2*)p16)[j] = make_uint2(pack_bf2(P[u][0], P[u][1]), pack_bf2(P[u][2], P[u][3]));
-          }
-        }
-      }
-      seg = pend;
-    }
-  }
-}
-
-}  // namespace
-
 extern "C" int hamt_optim_table(int rule, size_t n, float* p, float* g, float* m, float* v, void* p16, const int* ends, const float* hyp,
                                 const float* aux, int nparams, const float* gnorm_sq, float max_norm, float beta1, float beta2, float eps,
                                 int zero_grad, void* stream) {
@@ -507,8 +476,7 @@ extern "C" int hamt_optim_table(int rule, size_t n, float* p, float* g, float* m
                  (!has_v || ((uintptr_t)v % 16) == 0) && ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)aux % 16) == 0,
                  "hamt_optim_table: arenas and tables must be 16-byte aligned");
   if (n == 0) return HAMT_OK;
-  size_t b = (n / 4 + 1023) / 1024;              // adamw_table_kernel's geometry: 16-KiB chunks, at most 2 048 blocks sweeping together
-  const int nb = (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+  const int nb = chunk_grid(n, 2048);
   hipStream_t s = as_stream(stream);
 #define HAMT_OPTIM_LAUNCH(R)                                                                                                          \
   hipLaunchKernelGGL((optim_table_kernel<R, 4>), dim3(nb), dim3(256), 0, s, n, p, g, m, v, (bf16_t*)p16, ends, (const float4*)hyp,     \
