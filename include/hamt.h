@@ -33,7 +33,7 @@ extern "C" {
 
 #define HAMT_ABI_VERSION 2   /* 2 (round 6): hamt_gemm_ln_fwd / hamt_graph_split_* removed (round 5); hamt_embed_sum_bwd takes V and ws_bytes,
                               * hamt_scatter_add_rows_ordered takes T; hamt_wgrad_grouped_ex and the dtype HAMT_F16 added.  Entry points added since (the
-                              * policy / nav / eval families, hamt_attn_cls_fwd, hamt_image_resample) change no existing signature and leave the number at 2. */
+                              * policy / nav / obs / eval families, hamt_attn_cls_fwd, hamt_image_resample) change no existing signature and leave the number at 2. */
 
 typedef enum { HAMT_OK = 0, HAMT_ERR_ARG = -1, HAMT_ERR_UNSUPPORTED = -2, HAMT_ERR_LAUNCH = -3 } hamt_status;
 typedef enum { HAMT_F32 = 0, HAMT_BF16 = 1,
@@ -718,6 +718,37 @@ int hamt_nav_eval_goals(int N, int p_max, int e_max, int g_max, const double* di
 int hamt_nav_eval_back(int N, int p_max, int g_max, const double* dist, const int64_t* scan_off, const int32_t* scan_n,
                        const int32_t* scan, const int32_t* path, const int32_t* path_len, const int32_t* gt, const int32_t* gt_len,
                        const int32_t* midstop, const int32_t* gt_midstop, double* out, void* stream);
+/* The observations of a rollout step, gathered from a viewpoint store (csrc/obs.hip).  The store holds every viewpoint of every scan in
+ * the arena order of the navigation graphs, row = vp_base[scan] + local node (vp_base int64 = the prefix sum of scan_n), NV rows:
+ * feat fp32 [NV, 36, F]; ang36 fp32 [36, 36, A] (base view, view); cand_cnt int32 [NV]; cand_point int32 [NV, C] (each candidate's view
+ * index), cand_node int32 [NV, C] (its local node, -1 = padding), cand_ang fp32 [NV, C, 12, A] (its angle feature for each of the 12 base
+ * headings).  C above HAMT_OBS_MAX_CAND: HAMT_ERR_UNSUPPORTED, nothing launched.  Episode b: ep_scan[b], cur[b], view[b] in [0, 36).
+ *
+ * hamt_obs_gather: with row = vp_base[ep_scan[b]] + cur[b] and n = min(cand_cnt[row], C, W - 1), slot c < n of episode b is candidate c
+ * (image feat[row, cand_point[c]], angle cand_ang[row, c, view % 12], nav type 1), slot n is STOP (zeros, nav type 2); HAMT_OBS_PANO
+ * (agent_cmt.py::_cand_pano_feature_variable) goes on with the views no candidate points to, ascending (image feat[row, v], angle
+ * ang36[view, v], nav type 0); HAMT_OBS_CAND (::_candidate_variable) ends there.  The slots from ob_len[b] to W are zeros, nav type 0.
+ * ob_img fp32 [B, W, F], ob_ang fp32 [B, W, A], ob_nav int64 [B, W], ob_mask uint8 [B, W] (1 = slot < ob_len), ob_len, cand_len (= n + 1)
+ * int32 [B], cand_node_out / cand_point_out int32 [B, W] (the candidates' nodes / views, -1 elsewhere).  hist_img [B, F] = feat[row, view],
+ * hist_pano_img [B, 36, F] = feat[row], hist_pano_ang [B, 36, A] = ang36[view] (::_history_variable): each may be NULL.  Every element of
+ * every output is written by every call; ended episodes are gathered like the others.  A cur outside its scan or a view outside
+ * [0, 36): nothing is read from the store, the episode is STOP alone (zeros everywhere, nav type 2 and mask 1 in slot 0, ob_len =
+ * cand_len = 1, zero history rows), anomalies[0] += 1.  Rows are copied 16 bytes per lane when F % 4 == 0 and feat, ob_img, hist_img
+ * and hist_pano_img are 16-byte aligned, element by element otherwise; no arithmetic touches a value.
+ *
+ * hamt_obs_turn: view[b] = cand_point_out[b, env_action[b]] where 0 <= env_action[b] < W and that slot holds a candidate; unchanged
+ * otherwise.  view_log_row int32 [B] (may be NULL) receives the resulting views.  It reads what hamt_obs_gather wrote, not the store. */
+#define HAMT_OBS_PANO 0
+#define HAMT_OBS_CAND 1
+#define HAMT_OBS_MAX_CAND 64
+int hamt_obs_gather(int B, int W, int F, int A, int C, int layout, const float* feat, const float* ang36, const int32_t* cand_cnt,
+                    const int32_t* cand_point, const int32_t* cand_node, const float* cand_ang, const int64_t* vp_base,
+                    const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cur, const int32_t* view, float* ob_img,
+                    float* ob_ang, int64_t* ob_nav, uint8_t* ob_mask, int32_t* ob_len, int32_t* cand_len, int32_t* cand_node_out,
+                    int32_t* cand_point_out, float* hist_img, float* hist_pano_img, float* hist_pano_ang, int32_t* anomalies,
+                    void* stream);
+int hamt_obs_turn(int B, int W, const int32_t* cand_point_out, const int32_t* env_action, int32_t* view, int32_t* view_log_row,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

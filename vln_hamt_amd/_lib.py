@@ -183,6 +183,8 @@ SIGNATURES = {
     "hamt_nav_advance_back": [i32, i32, i32, i32, i32] + [vp] * 23,
     "hamt_nav_eval_goals": [i32, i32, i32, i32] + [vp] * 12,
     "hamt_nav_eval_back": [i32, i32, i32] + [vp] * 12,
+    "hamt_obs_gather": [i32, i32, i32, i32, i32, i32] + [vp] * 24,
+    "hamt_obs_turn": [i32, i32] + [vp] * 5,
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

@@ -11,7 +11,8 @@ With `nav=` (agent.NavEpisodes: the episodes' place in the navigation graph, on 
 teacher action lookup (`_teacher_action`, :199-211), the back-track mask (:342-349) and the reward shaping
 (:407-445) run on the device too, and the reward lands in row t of `reward`.
 
-What stays on the host: the simulator (and, without `nav=`, the teacher action lookup and the reward shaping, handed in by the caller).
+What stays on the host: the simulator (and, without `nav=`, the teacher action lookup and the reward shaping, handed in by the caller;
+the observations the model reads come from the host too unless an `agent.ObsEpisodes` gathers them on the device).
 """
 from __future__ import annotations
 

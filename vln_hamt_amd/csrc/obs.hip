@@ -1,0 +1,162 @@
+// The observations a finetune rollout step feeds the model, gathered on the device from a viewpoint store:
+//   obs_gather  what finetune_src/r2r/env.py::_get_obs (make_candidate's cached branch, :239-252) and the agent's
+//               _cand_pano_feature_variable (agent_cmt.py:104-151), _candidate_variable (:153-171) and _history_variable (:173-190)
+//               build on the host: candidates first, STOP, then (HAMT_OBS_PANO) the views no candidate points to, padding after them;
+//   obs_turn    the view index after a move: the chosen candidate's pointId (make_equiv_action, :213-246).
+// With discretised viewing angles an observation is a pure function of (scan, viewpoint, view index): the store holds every viewpoint of
+// every scan in the arena order of the navigation graphs, row = vp_base[scan] + local node.  A pure gather: no arithmetic on a feature
+// value, so every output is exact.  One wave per output row; each wave builds its episode's slot-to-source map itself (the 36-bit mask of
+// candidate views by an OR over lanes, the rank of a free view by a population count) and copies the row with 16 bytes per lane when
+// F % 4 == 0 and the bases are aligned, element by element otherwise (and for the A-wide angle rows).  Wave shuffles only: no LDS, no
+// hand-off between waves; the only atomic is the anomaly counter.  Offsets into feat are 64-bit.
+#include "common.h"
+
+namespace {
+
+constexpr int kWaves = 4;                          // rows per 256-thread workgroup
+constexpr int kViews = 36;
+constexpr int kHeadings = 12;
+constexpr int kMaxRowBlocks = 64;                  // row blocks per episode; more rows than 64 * kWaves are strided over
+
+__device__ __forceinline__ uint32_t wave_or_u(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+// dst[0..n) = src[0..n), or zeros for a NULL src
+__device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* __restrict__ src, int n, bool vec, int lane) {
+  if (vec) {
+    f32x4* __restrict__ d = reinterpret_cast<f32x4*>(dst);
+    const f32x4* __restrict__ s = reinterpret_cast<const f32x4*>(src);
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = lane; i < (n >> 2); i += 64) d[i] = src ? s[i] : zero;
+  } else {
+    for (int i = lane; i < n; i += 64) dst[i] = src ? src[i] : 0.0f;
+  }
+}
+
+__global__ __launch_bounds__(64 * kWaves) void obs_gather_kernel(
+    int B, int W, int F, int A, int C, int layout, int vec, const float* __restrict__ feat, const float* __restrict__ ang36,
+    const int32_t* __restrict__ cand_cnt, const int32_t* __restrict__ cand_point, const int32_t* __restrict__ cand_node,
+    const float* __restrict__ cand_ang, const int64_t* __restrict__ vp_base, const int32_t* __restrict__ scan_n,
+    const int32_t* __restrict__ ep_scan, const int32_t* __restrict__ cur, const int32_t* __restrict__ view, float* __restrict__ ob_img,
+    float* __restrict__ ob_ang, int64_t* __restrict__ ob_nav, uint8_t* __restrict__ ob_mask, int32_t* __restrict__ ob_len,
+    int32_t* __restrict__ cand_len, int32_t* __restrict__ cand_node_out, int32_t* __restrict__ cand_point_out, float* __restrict__ hist_img,
+    float* __restrict__ hist_pano_img, float* __restrict__ hist_pano_ang, int32_t* anomalies) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x;
+  const int rows = W + ((hist_img || hist_pano_img || hist_pano_ang) ? 1 + kViews : 0);
+
+  // ---- the episode's slot-to-source map (every wave, in registers)
+  const int s = ep_scan[b], here = cur[b], vw = view[b];
+  const bool ok = here >= 0 && here < scan_n[s] && vw >= 0 && vw < kViews;
+  const int64_t row = ok ? vp_base[s] + (int64_t)here : 0;
+  const int n = ok ? min(max(cand_cnt[row], 0), min(C, W - 1)) : 0;                  // navigable candidates; slot n is STOP
+  const int pt = lane < n ? min(max(cand_point[row * C + lane], 0), kViews - 1) : -1;  // candidate `lane`'s view
+  const uint32_t lo = wave_or_u(pt >= 0 && pt < 32 ? 1u << pt : 0u), hi = wave_or_u(pt >= 32 ? 1u << (pt - 32) : 0u);
+  const uint64_t taken = ((uint64_t)hi << 32) | lo;                                  // (two candidates may share a view: one bit)
+  const uint64_t free_views = (ok && layout == HAMT_OBS_PANO) ? ~taken & ((1ull << kViews) - 1) : 0ull;
+  const int len = min(n + 1 + __popcll(free_views), W);
+  const bool is_free = lane < kViews && ((free_views >> lane) & 1ull);
+  const int rank = __popcll(free_views & ((1ull << lane) - 1ull));                    // free views below view `lane`
+  const float* frow = feat + row * (int64_t)kViews * F;                               // feat[row]
+
+  for (int r = blockIdx.y * kWaves + (threadIdx.x >> 6); r < rows; r += gridDim.y * kWaves) {      // (r is wave-uniform)
+    if (r < W) {
+      const int64_t o = (int64_t)b * W + r;
+      const float *img = nullptr, *ang = nullptr;
+      int nav = 0, node = -1, point = -1;
+      if (r < n) {                                                                   // a candidate, in table order
+        point = __shfl(pt, r, 64);
+        node = cand_node[row * C + r];
+        img = frow + (int64_t)point * F;
+        ang = cand_ang + ((row * C + r) * kHeadings + vw % kHeadings) * A;
+        nav = 1;
+      } else if (r == n) {                                                           // STOP: zeros
+        nav = 2;
+      } else if (r < len) {                                                          // the (r - n - 1)-th view no candidate points to
+        const int v = max(__ffsll((unsigned long long)__ballot(is_free && rank == r - n - 1)) - 1, 0);
+        img = frow + (int64_t)v * F;
+        ang = ang36 + ((int64_t)vw * kViews + v) * A;
+      }
+      copy_row(ob_img + o * F, img, F, vec != 0, lane);
+      copy_row(ob_ang + o * A, ang, A, false, lane);
+      if (lane == 0) {
+        ob_nav[o] = nav;
+        ob_mask[o] = r < len ? 1 : 0;
+        cand_node_out[o] = node;
+        cand_point_out[o] = point;
+        if (r == 0) {
+          ob_len[b] = len;
+          cand_len[b] = n + 1;
+          if (!ok) atomicAdd(&anomalies[0], 1);
+        }
+      }
+    } else if (r == W) {                                                             // the view looked at (_history_variable)
+      if (hist_img) copy_row(hist_img + (int64_t)b * F, ok ? frow + (int64_t)vw * F : nullptr, F, vec != 0, lane);
+    } else {                                                                         // the whole panorama, relative to that view
+      const int v = r - W - 1;
+      const int64_t o = (int64_t)b * kViews + v;
+      if (hist_pano_img) copy_row(hist_pano_img + o * F, ok ? frow + (int64_t)v * F : nullptr, F, vec != 0, lane);
+      if (hist_pano_ang) copy_row(hist_pano_ang + o * A, ok ? ang36 + ((int64_t)vw * kViews + v) * A : nullptr, A, false, lane);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void obs_turn_kernel(int B, int W, const int32_t* __restrict__ cand_point_out,
+                                                       const int32_t* __restrict__ env_action, int32_t* __restrict__ view,
+                                                       int32_t* __restrict__ view_log_row) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int a = env_action[b];
+  int v = view[b];
+  if (a >= 0 && a < W) {
+    const int p = cand_point_out[(int64_t)b * W + a];
+    if (p >= 0 && p < kViews) v = p;                        // (a padding slot: no move, the view stays)
+  }
+  view[b] = v;
+  if (view_log_row) view_log_row[b] = v;
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+}  // namespace
+
+extern "C" int hamt_obs_gather(int B, int W, int F, int A, int C, int layout, const float* feat, const float* ang36, const int32_t* cand_cnt,
+                               const int32_t* cand_point, const int32_t* cand_node, const float* cand_ang, const int64_t* vp_base,
+                               const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cur, const int32_t* view, float* ob_img,
+                               float* ob_ang, int64_t* ob_nav, uint8_t* ob_mask, int32_t* ob_len, int32_t* cand_len, int32_t* cand_node_out,
+                               int32_t* cand_point_out, float* hist_img, float* hist_pano_img, float* hist_pano_ang, int32_t* anomalies,
+                               void* stream) {
+  HAMT_CHECK_ARG(B >= 0 && W > 0 && F > 0 && A > 0 && C > 0, "hamt_obs_gather: need W, F, A, C > 0");
+  HAMT_CHECK_ARG(layout == HAMT_OBS_PANO || layout == HAMT_OBS_CAND, "hamt_obs_gather: bad layout");
+  if (C > HAMT_OBS_MAX_CAND) {
+    hamt_set_error("hamt_obs_gather: C %d above %d", C, HAMT_OBS_MAX_CAND);
+    return HAMT_ERR_UNSUPPORTED;
+  }
+  HAMT_CHECK_ARG(feat && ang36 && cand_cnt && cand_point && cand_node && cand_ang && vp_base && scan_n && ep_scan && cur && view && ob_img &&
+                     ob_ang && ob_nav && ob_mask && ob_len && cand_len && cand_node_out && cand_point_out && anomalies,
+                 "hamt_obs_gather: null pointer");
+  if (B == 0) return HAMT_OK;
+  const int rows = W + ((hist_img || hist_pano_img || hist_pano_ang) ? 1 + 36 : 0);
+  const int row_blocks = (rows + kWaves - 1) / kWaves;
+  const int vec = F % 4 == 0 && aligned16(feat) && aligned16(ob_img) && aligned16(hist_img) && aligned16(hist_pano_img);
+  hipLaunchKernelGGL(obs_gather_kernel, dim3(B, row_blocks < kMaxRowBlocks ? row_blocks : kMaxRowBlocks), dim3(64 * kWaves), 0,
+                     as_stream(stream), B, W, F, A, C, layout, vec, feat, ang36, cand_cnt, cand_point, cand_node, cand_ang, vp_base, scan_n,
+                     ep_scan, cur, view, ob_img, ob_ang, ob_nav, ob_mask, ob_len, cand_len, cand_node_out, cand_point_out, hist_img,
+                     hist_pano_img, hist_pano_ang, anomalies);
+  HAMT_CHECK_LAUNCH("hamt_obs_gather");
+  return HAMT_OK;
+}
+
+extern "C" int hamt_obs_turn(int B, int W, const int32_t* cand_point_out, const int32_t* env_action, int32_t* view, int32_t* view_log_row,
+                             void* stream) {
+  HAMT_CHECK_ARG(B >= 0 && W > 0, "hamt_obs_turn: need W > 0");
+  HAMT_CHECK_ARG(cand_point_out && env_action && view, "hamt_obs_turn: null pointer");
+  if (B == 0) return HAMT_OK;
+  hipLaunchKernelGGL(obs_turn_kernel, dim3((B + 255) / 256), dim3(256), 0, as_stream(stream), B, W, cand_point_out, env_action, view,
+                     view_log_row);
+  HAMT_CHECK_LAUNCH("hamt_obs_turn");
+  return HAMT_OK;
+}

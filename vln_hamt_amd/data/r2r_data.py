@@ -187,6 +187,10 @@ class ViewFeatureStore:
                 self._cache[key] = fts
         return fts
 
+    def get_image_feature(self, scan, viewpoint) -> np.ndarray:
+        """the block of one viewpoint by (scan, viewpoint), as MultiStepNavData.get_image_feature reads it"""
+        return self.get(f"{scan}_{viewpoint}")
+
 
 # ------------------------------------------------------------------------------------------------ the dataset
 class MultiStepNavData(object):

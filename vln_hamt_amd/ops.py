@@ -1661,6 +1661,61 @@ def nav_eval_back(graphs, scan, path, path_len, gt, gt_len, midstop, gt_midstop)
     return out
 
 
+OBS_LAYOUTS = {"pano": 0, "cand": 1}                          # HAMT_OBS_*
+OBS_MAX_CAND = 64                                             # HAMT_OBS_MAX_CAND
+OBS_VIEWS = 36
+
+
+def obs_gather(store, ep_scan, cur, view, out, anomalies, layout="pano"):
+    """The observations of one rollout step, one launch (csrc/obs.hip): for the B episodes standing on node `cur` int32 [B] of scan
+    `ep_scan` int32 [B] (an agent.NavEpisodes' tensors) and looking at `view` int32 [B], what env.py::_get_obs and the agent's
+    _cand_pano_feature_variable (`layout` 'pano') or _candidate_variable ('cand') and _history_variable build on the host, gathered
+    from `store` (an agent.ObsStore: feat, ang36, cand_cnt, cand_point, cand_node, cand_ang, vp_base, scan_n on the device).
+    `out` carries the buffers, every element of which is overwritten: ob_img fp32 [B, W, F], ob_ang fp32 [B, W, A], ob_nav int64 [B, W],
+    ob_mask uint8 [B, W], ob_len / cand_len int32 [B], cand_nodes / cand_points int32 [B, W], and hist_img [B, F], hist_pano_img
+    [B, 36, F], hist_pano_ang [B, 36, A] or None.  An episode outside its scan or its 36 views becomes STOP alone and adds 1 to
+    `anomalies` int32 [>= 1].  Nothing is read from the host."""
+    _chk(out.ob_img, "obs_gather")
+    dev, (B, W, F), A, C = out.ob_img.device, out.ob_img.shape, out.ob_ang.shape[-1], store.cand_point.shape[1]
+    NV = store.feat.shape[0]
+    for name, t_, dt, shape in (("feat", store.feat, torch.float32, (NV, OBS_VIEWS, F)), ("ang36", store.ang36, torch.float32, (OBS_VIEWS, OBS_VIEWS, A)),
+                                ("cand_cnt", store.cand_cnt, torch.int32, (NV,)), ("cand_point", store.cand_point, torch.int32, (NV, C)),
+                                ("cand_node", store.cand_node, torch.int32, (NV, C)), ("cand_ang", store.cand_ang, torch.float32, (NV, C, 12, A)),
+                                ("vp_base", store.vp_base, torch.int64, store.scan_n.shape), ("scan_n", store.scan_n, torch.int32, store.scan_n.shape),
+                                ("ep_scan", ep_scan, torch.int32, (B,)), ("cur", cur, torch.int32, (B,)), ("view", view, torch.int32, (B,)),
+                                ("ob_img", out.ob_img, torch.float32, (B, W, F)), ("ob_ang", out.ob_ang, torch.float32, (B, W, A)),
+                                ("ob_nav", out.ob_nav, torch.int64, (B, W)), ("ob_mask", out.ob_mask, torch.uint8, (B, W)),
+                                ("ob_len", out.ob_len, torch.int32, (B,)), ("cand_len", out.cand_len, torch.int32, (B,)),
+                                ("cand_nodes", out.cand_nodes, torch.int32, (B, W)), ("cand_points", out.cand_points, torch.int32, (B, W)),
+                                ("hist_img", out.hist_img, torch.float32, (B, F)), ("hist_pano_img", out.hist_pano_img, torch.float32, (B, OBS_VIEWS, F)),
+                                ("hist_pano_ang", out.hist_pano_ang, torch.float32, (B, OBS_VIEWS, A))):
+        if t_ is not None:
+            _nav_arg("obs_gather: " + name, t_, dt, shape, dev)
+    if anomalies.dtype != torch.int32 or anomalies.device != dev or anomalies.numel() < 1:
+        raise L.HamtError("obs_gather: anomalies must be an int32 tensor on the outputs' device")
+    L.check(L.load().hamt_obs_gather(B, W, F, A, C, OBS_LAYOUTS[layout], _p(store.feat), _p(store.ang36), _p(store.cand_cnt), _p(store.cand_point),
+                                     _p(store.cand_node), _p(store.cand_ang), _p(store.vp_base), _p(store.scan_n), _p(ep_scan), _p(cur), _p(view),
+                                     _p(out.ob_img), _p(out.ob_ang), _p(out.ob_nav), _p(out.ob_mask), _p(out.ob_len), _p(out.cand_len),
+                                     _p(out.cand_nodes), _p(out.cand_points), _p(out.hist_img), _p(out.hist_pano_img), _p(out.hist_pano_ang),
+                                     _p(anomalies), _stream()), "hamt_obs_gather")
+    return out
+
+
+def obs_turn(cand_points, env_action, view, view_log_row=None):
+    """After the policy step, one launch: `view` int32 [B] becomes the chosen candidate's view index, `cand_points[b, env_action[b]]`
+    (what `obs_gather` wrote; make_equiv_action, agent_cmt.py:213-246), where `env_action` int32 [B] is >= 0; a stop (-1) leaves it.
+    `view_log_row` int32 [B] receives the resulting views."""
+    _chk(cand_points, "obs_turn")
+    dev, (B, W) = cand_points.device, cand_points.shape
+    _nav_arg("obs_turn: cand_points", cand_points, torch.int32, (B, W), dev)
+    _nav_arg("obs_turn: env_action", env_action, torch.int32, (B,), dev)
+    _nav_arg("obs_turn: view", view, torch.int32, (B,), dev)
+    if view_log_row is not None:
+        _nav_arg("obs_turn: view_log_row", view_log_row, torch.int32, (B,), dev)
+    L.check(L.load().hamt_obs_turn(B, W, _p(cand_points), _p(env_action), _p(view), _p(view_log_row), _stream()), "hamt_obs_turn")
+    return view
+
+
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
 
