@@ -749,6 +749,28 @@ int hamt_obs_gather(int B, int W, int F, int A, int C, int layout, const float* 
                     void* stream);
 int hamt_obs_turn(int B, int W, const int32_t* cand_point_out, const int32_t* env_action, int32_t* view, int32_t* view_log_row,
                   void* stream);
+/* REVERIE's candidate objects of a rollout step, gathered from an object store over the SAME arena rows (csrc/obs.hip; what
+ * finetune_src/reverie/env.py::_get_obs :181-215 and reverie/agent.py::_object_variable :125-139 build on the host).  The store is CSR:
+ * obj_off int64 [NV + 1] (row r owns the objects [obj_off[r], obj_off[r + 1]), already cut to the environment's max_objects; a viewpoint
+ * without objects owns none), obj_feat fp32 [NObj, Fo], obj_view int32 [NObj] (the view each object was seen in), obj_pos fp32 [NObj, 5]
+ * (reverie/data_utils.py::get_obj_local_pos), obj_id int32 [NObj] (>= 0).  ang36, vp_base, scan_n (S scans): the viewpoint store's.
+ *
+ * hamt_obj_gather: with row = vp_base[ep_scan[b]] + cur[b] and n = min(obj_off[row + 1] - obj_off[row], Ow), slot k < n of episode b is
+ * object obj_off[row] + k: obj_feats fp32 [B, Ow, Fo] = its obj_feat row, obj_angles fp32 [B, Ow, A] = ang36[view[b], obj_view] (view NOT
+ * reduced mod 12; obj_view clamped to [0, 36)), obj_poses fp32 [B, Ow, 5] = its obj_pos row, obj_ids int32 [B, Ow] = its id.  The slots
+ * from n to Ow are zeros, id -1.  obj_masks uint8 [B, Ow] = 1 for k < max(n, 1): a viewpoint without objects shows the model ONE live,
+ * all-zero slot (agent.py:126); obj_lens int32 [B] = n, the TRUE count hamt_policy_ref_step_fwd's obj_len wants.  Every element of every
+ * output is written by every call; ended episodes are gathered like the others.  An ep_scan outside [0, S), a cur outside its scan, a
+ * view outside [0, 36), or a row whose offsets leave [0, NObj] or descend: nothing is read from the object tables, the episode gets one
+ * live zero slot, obj_lens = 0, ids -1, anomalies[0] += 1.  Ow above HAMT_OBJ_MAX_WIDTH (hamt_policy_ref_step's limit on O):
+ * HAMT_ERR_UNSUPPORTED, nothing launched.  Rows are copied 16 bytes per lane when Fo % 4 == 0 and obj_feat and obj_feats are 16-byte
+ * aligned, element by element otherwise; offsets into obj_feat are 64-bit; no arithmetic touches a value. */
+#define HAMT_OBJ_MAX_WIDTH 256
+int hamt_obj_gather(int B, int Ow, int Fo, int A, int S, int64_t NV, int64_t NObj, const int64_t* obj_off, const float* obj_feat,
+                    const int32_t* obj_view, const float* obj_pos, const int32_t* obj_id, const float* ang36, const int64_t* vp_base,
+                    const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cur, const int32_t* view, float* obj_feats,
+                    float* obj_angles, float* obj_poses, uint8_t* obj_masks, int32_t* obj_lens, int32_t* obj_ids, int32_t* anomalies,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

@@ -185,6 +185,7 @@ SIGNATURES = {
     "hamt_nav_eval_back": [i32, i32, i32] + [vp] * 12,
     "hamt_obs_gather": [i32, i32, i32, i32, i32, i32] + [vp] * 24,
     "hamt_obs_turn": [i32, i32] + [vp] * 5,
+    "hamt_obj_gather": [i32, i32, i32, i32, i32, C.c_int64, C.c_int64] + [vp] * 19,
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

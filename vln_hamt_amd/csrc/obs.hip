@@ -2,7 +2,10 @@
 //   obs_gather  what finetune_src/r2r/env.py::_get_obs (make_candidate's cached branch, :239-252) and the agent's
 //               _cand_pano_feature_variable (agent_cmt.py:104-151), _candidate_variable (:153-171) and _history_variable (:173-190)
 //               build on the host: candidates first, STOP, then (HAMT_OBS_PANO) the views no candidate points to, padding after them;
-//   obs_turn    the view index after a move: the chosen candidate's pointId (make_equiv_action, :213-246).
+//   obs_turn    the view index after a move: the chosen candidate's pointId (make_equiv_action, :213-246);
+//   obj_gather  REVERIE's candidate objects of the viewpoint stood on (finetune_src/reverie/env.py:181-215 and the agent's
+//               _object_variable, reverie/agent.py:125-139), from a CSR object store over the same arena rows: features, the angle
+//               feature of the view each object was seen in, normalised boxes, mask, true count and ids, zeros and -1 in the padding.
 // With discretised viewing angles an observation is a pure function of (scan, viewpoint, view index): the store holds every viewpoint of
 // every scan in the arena order of the navigation graphs, row = vp_base[scan] + local node.  A pure gather: no arithmetic on a feature
 // value, so every output is exact.  One wave per output row; each wave builds its episode's slot-to-source map itself (the 36-bit mask of
@@ -119,9 +122,79 @@ __global__ __launch_bounds__(256) void obs_turn_kernel(int B, int W, const int32
   if (view_log_row) view_log_row[b] = v;
 }
 
+// One wave per output row (b, k): object k of the viewpoint episode b stands on, or a padding row.
+__global__ __launch_bounds__(64 * kWaves) void obj_gather_kernel(
+    int B, int Ow, int Fo, int A, int S, int64_t NV, int64_t NObj, int vec, const int64_t* __restrict__ obj_off,
+    const float* __restrict__ obj_feat, const int32_t* __restrict__ obj_view, const float* __restrict__ obj_pos,
+    const int32_t* __restrict__ obj_id, const float* __restrict__ ang36, const int64_t* __restrict__ vp_base,
+    const int32_t* __restrict__ scan_n, const int32_t* __restrict__ ep_scan, const int32_t* __restrict__ cur,
+    const int32_t* __restrict__ view, float* __restrict__ obj_feats, float* __restrict__ obj_angles, float* __restrict__ obj_poses,
+    uint8_t* __restrict__ obj_masks, int32_t* __restrict__ obj_lens, int32_t* __restrict__ obj_ids, int32_t* anomalies) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x;
+
+  // ---- the episode's slice of the store (every wave, in registers)
+  const int s = ep_scan[b], here = cur[b], vw = view[b];
+  bool ok = s >= 0 && s < S && vw >= 0 && vw < kViews;
+  ok = ok && here >= 0 && here < scan_n[s];
+  const int64_t row = ok ? vp_base[s] + (int64_t)here : 0;
+  ok = ok && row >= 0 && row < NV;
+  const int64_t first = ok ? obj_off[row] : 0, last = ok ? obj_off[row + 1] : 0;
+  ok = ok && first >= 0 && first <= last && last <= NObj;                            // (a store that contradicts itself: an anomaly too)
+  const int n = ok ? (int)min(last - first, (int64_t)Ow) : 0;                        // the true count
+  const int live = max(n, 1);                                                        // (_object_variable: an empty viewpoint keeps one zero slot)
+
+  for (int k = blockIdx.y * kWaves + (threadIdx.x >> 6); k < Ow; k += gridDim.y * kWaves) {      // (k is wave-uniform)
+    const int64_t o = (int64_t)b * Ow + k, src = first + k;
+    const float *fts = nullptr, *ang = nullptr, *pos = nullptr;
+    int id = -1;
+    if (k < n) {
+      fts = obj_feat + src * Fo;
+      ang = ang36 + ((int64_t)vw * kViews + min(max(obj_view[src], 0), kViews - 1)) * A;
+      pos = obj_pos + src * 5;
+      id = obj_id[src];
+    }
+    copy_row(obj_feats + o * Fo, fts, Fo, vec != 0, lane);
+    copy_row(obj_angles + o * A, ang, A, false, lane);
+    copy_row(obj_poses + o * 5, pos, 5, false, lane);
+    if (lane == 0) {
+      obj_masks[o] = k < live ? 1 : 0;
+      obj_ids[o] = id;
+      if (k == 0) {
+        obj_lens[b] = n;
+        if (!ok) atomicAdd(&anomalies[0], 1);
+      }
+    }
+  }
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
+
+extern "C" int hamt_obj_gather(int B, int Ow, int Fo, int A, int S, int64_t NV, int64_t NObj, const int64_t* obj_off, const float* obj_feat,
+                               const int32_t* obj_view, const float* obj_pos, const int32_t* obj_id, const float* ang36,
+                               const int64_t* vp_base, const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cur,
+                               const int32_t* view, float* obj_feats, float* obj_angles, float* obj_poses, uint8_t* obj_masks,
+                               int32_t* obj_lens, int32_t* obj_ids, int32_t* anomalies, void* stream) {
+  HAMT_CHECK_ARG(B >= 0 && Ow > 0 && Fo > 0 && A > 0 && S > 0 && NV >= 0 && NObj >= 0, "hamt_obj_gather: need Ow, Fo, A, S > 0");
+  if (Ow > HAMT_OBJ_MAX_WIDTH) {
+    hamt_set_error("hamt_obj_gather: Ow %d above %d", Ow, HAMT_OBJ_MAX_WIDTH);
+    return HAMT_ERR_UNSUPPORTED;
+  }
+  HAMT_CHECK_ARG(obj_off && (obj_feat || NObj == 0) && (obj_view || NObj == 0) && (obj_pos || NObj == 0) && (obj_id || NObj == 0) && ang36 &&
+                     vp_base && scan_n && ep_scan && cur && view && obj_feats && obj_angles && obj_poses && obj_masks && obj_lens && obj_ids &&
+                     anomalies,
+                 "hamt_obj_gather: null pointer");
+  if (B == 0) return HAMT_OK;
+  const int row_blocks = (Ow + kWaves - 1) / kWaves;
+  const int vec = Fo % 4 == 0 && aligned16(obj_feat) && aligned16(obj_feats);
+  hipLaunchKernelGGL(obj_gather_kernel, dim3(B, row_blocks < kMaxRowBlocks ? row_blocks : kMaxRowBlocks), dim3(64 * kWaves), 0,
+                     as_stream(stream), B, Ow, Fo, A, S, NV, NObj, vec, obj_off, obj_feat, obj_view, obj_pos, obj_id, ang36, vp_base, scan_n,
+                     ep_scan, cur, view, obj_feats, obj_angles, obj_poses, obj_masks, obj_lens, obj_ids, anomalies);
+  HAMT_CHECK_LAUNCH("hamt_obj_gather");
+  return HAMT_OK;
+}
 
 extern "C" int hamt_obs_gather(int B, int W, int F, int A, int C, int layout, const float* feat, const float* ang36, const int32_t* cand_cnt,
                                const int32_t* cand_point, const int32_t* cand_node, const float* cand_ang, const int64_t* vp_base,

@@ -1716,6 +1716,41 @@ def obs_turn(cand_points, env_action, view, view_log_row=None):
     return view
 
 
+OBJ_MAX_WIDTH = 256                                           # HAMT_OBJ_MAX_WIDTH (policy_ref_step's limit on O)
+
+
+def obj_gather(store, ep_scan, cur, view, out, anomalies):
+    """REVERIE's candidate objects of one rollout step, one launch (csrc/obs.hip): for the B episodes standing on node `cur` int32 [B]
+    of scan `ep_scan` int32 [B] and looking at `view` int32 [B], what reverie/env.py::_get_obs (:181-215) and the agent's
+    _object_variable (reverie/agent.py:125-139) build on the host, gathered from `store` (an agent.ObjStore: obj_off, obj_feat, obj_view,
+    obj_pos, obj_id, and its viewpoint store's ang36, vp_base, scan_n, on the device).  `out` carries the buffers, every element of which
+    is overwritten: obj_feats fp32 [B, Ow, Fo], obj_angles fp32 [B, Ow, A], obj_poses fp32 [B, Ow, 5], obj_masks uint8 [B, Ow] (one live
+    slot at a viewpoint without objects), obj_lens int32 [B] (the true count), obj_ids int32 [B, Ow] (-1 = padding).  An episode
+    outside its scan or its 36 views gets one live zero slot, count 0, and adds 1 to `anomalies` int32 [>= 1].  Nothing is read from
+    the host."""
+    _chk(out.obj_feats, "obj_gather")
+    dev, (B, Ow, Fo), A = out.obj_feats.device, out.obj_feats.shape, out.obj_angles.shape[-1]
+    NV, NObj, S = store.obj_off.shape[0] - 1, store.obj_feat.shape[0], store.scan_n.shape[0]
+    if Ow > OBJ_MAX_WIDTH:
+        raise L.HamtError(f"obj_gather: {Ow} object slots, above the supported {OBJ_MAX_WIDTH}")
+    for name, t_, dt, shape in (("obj_off", store.obj_off, torch.int64, (NV + 1,)), ("obj_feat", store.obj_feat, torch.float32, (NObj, Fo)),
+                                ("obj_view", store.obj_view, torch.int32, (NObj,)), ("obj_pos", store.obj_pos, torch.float32, (NObj, 5)),
+                                ("obj_id", store.obj_id, torch.int32, (NObj,)), ("ang36", store.ang36, torch.float32, (OBS_VIEWS, OBS_VIEWS, A)),
+                                ("vp_base", store.vp_base, torch.int64, (S,)), ("scan_n", store.scan_n, torch.int32, (S,)),
+                                ("ep_scan", ep_scan, torch.int32, (B,)), ("cur", cur, torch.int32, (B,)), ("view", view, torch.int32, (B,)),
+                                ("obj_feats", out.obj_feats, torch.float32, (B, Ow, Fo)), ("obj_angles", out.obj_angles, torch.float32, (B, Ow, A)),
+                                ("obj_poses", out.obj_poses, torch.float32, (B, Ow, 5)), ("obj_masks", out.obj_masks, torch.uint8, (B, Ow)),
+                                ("obj_lens", out.obj_lens, torch.int32, (B,)), ("obj_ids", out.obj_ids, torch.int32, (B, Ow))):
+        _nav_arg("obj_gather: " + name, t_, dt, shape, dev)
+    if anomalies.dtype != torch.int32 or anomalies.device != dev or anomalies.numel() < 1:
+        raise L.HamtError("obj_gather: anomalies must be an int32 tensor on the outputs' device")
+    L.check(L.load().hamt_obj_gather(B, Ow, Fo, A, S, NV, NObj, _p(store.obj_off), _p(store.obj_feat), _p(store.obj_view), _p(store.obj_pos),
+                                     _p(store.obj_id), _p(store.ang36), _p(store.vp_base), _p(store.scan_n), _p(ep_scan), _p(cur), _p(view),
+                                     _p(out.obj_feats), _p(out.obj_angles), _p(out.obj_poses), _p(out.obj_masks), _p(out.obj_lens),
+                                     _p(out.obj_ids), _p(anomalies), _stream()), "hamt_obj_gather")
+    return out
+
+
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
 
