@@ -287,7 +287,7 @@ def test_unzeroed_weight_gradient_slots_do_not_leak(tiny, monkeypatch):
     parameter).  A head that trained in step t and has no gradient in step t+1 then still holds step t's gradient in its slot:
     neither the global norm (hamt_sumsq_table: active parameters only) nor the update may see it, and when the head trains
     again its slot is overwritten, not accumulated into.  Same trajectory as with every slot zeroed (HAMT_ZERO_ALL_GRADS)."""
-    from vln_hamt_amd.optim import adamw as A
+    from vln_hamt_amd.optim import arena as A       # (the module whose _build reads KEEP_GRAD)
     from vln_hamt_amd.optim import clip_grad_norm_
     from vln_hamt_amd.synth import make_batch
     _, cfg, sd = tiny

@@ -403,6 +403,58 @@ def test_checkpoint_reload_is_bit_identical(rule):
     assert same_bits(opt._flat_p16, opt2._flat_p16)
 
 
+@pytest.mark.parametrize("name", ["AdamW", "RangerLars", "TorchAdamW"])
+def test_resume_inside_a_dropped_pass_forgets_the_counted_step(name):
+    """A resume inside a NaN guard: backward, clip_grad_norm_ (which counts the step), load_state_dict, zero_grad().  The counted step
+    belongs to the counts the load replaced: zero_grad() must not take it back from the LOADED counts, and the next step must build its
+    own table.  Eight bare parameters in two groups (_adamw_ref.PY_SHAPES: a GEMM weight in the shadow region, a 5x7 and a 1-element
+    tensor behind alignment gaps); `a` takes three steps and saves, `b` resumes from it as above over clones of a's parameters; two
+    further steps leave every arena of the two equal bit for bit."""
+    from vln_hamt_amd import optim
+    pc = A.py_case()
+
+    def make(init):
+        params = [torch.nn.Parameter(t) for t in init]
+        groups = [{"params": [p for p, g in zip(params, A.PY_GROUP) if g == k], "weight_decay": A.PY_WD[k]} for k in (0, 1)]
+        return params, {"AdamW": lambda: optim.AdamW(groups, lr=1e-3), "RangerLars": lambda: optim.RangerLars(groups, alpha=0.5, k=2, lr=1e-3),
+                        "TorchAdamW": lambda: optim.TorchAdamW(groups, lr=1e-3)}[name]()
+
+    def backward(params, s):
+        for p, g in zip(params, pc["grads"][s]):
+            p.grad = None if g is None else torch.from_numpy(g).to(DEV)
+
+    def step(params, opt, s):
+        for k, grp in enumerate(opt.param_groups):
+            grp["lr"] = A.PY_LR[s][k]
+        backward(params, s)
+        optim.clip_grad_norm_(params, A.PY_MAX_NORM, optimizer=opt)
+        opt.step()
+        opt.zero_grad()
+
+    pa, a = make([torch.from_numpy(x.copy()).to(DEV) for x in pc["init"]])
+    for s in range(3):
+        step(pa, a, s)
+    sd = copy.deepcopy(a.state_dict())
+    pb, b = make([p.detach().clone() for p in pa])
+    backward(pb, 3)
+    optim.clip_grad_norm_(pb, A.PY_MAX_NORM, optimizer=b)
+    assert b._counted is not None and b._steps.sum() == len(pb)           # the step is counted
+    b.load_state_dict(sd)
+    b.zero_grad()
+    want = [1 if i in A.PY_LAG else 3 for i in range(len(pa))]          # (PY_LAG: no gradient in steps 2 and 3)
+    assert [int(a._steps[a._index_of[id(p)]]) for p in pa] == want
+    assert b._steps.tolist() == a._steps.tolist()
+    for s in (3, 4):
+        step(pa, a, s)
+        step(pb, b, s)
+    torch.cuda.synchronize()
+    assert b._steps.tolist() == a._steps.tolist()
+    for k in ("_flat_p", "_flat_m", "_flat_v", "_flat_p16") + (("_flat_slow",) if name == "RangerLars" else ()):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    if name == "RangerLars":
+        assert a._has_slow.tolist() == b._has_slow.tolist() and a._has_slow.any()
+
+
 @pytest.mark.parametrize("int_step", [False, True], ids=["tensor_step", "int_step"])
 @pytest.mark.parametrize("rule", [R.ADAMW, R.RMSPROP], ids=_ids)
 def test_checkpoint_moves_to_and_from_torch(rule, int_step):

@@ -223,11 +223,11 @@ def _params():
 
 def test_constructor_defaults_are_torchs():
     from vln_hamt_amd import _lib as L
-    from vln_hamt_amd.optim import AdamW
+    from vln_hamt_amd.optim import AdamW, ArenaOptimizer
     for rule, cls in _classes().items():
         kw = dict(lr=0.1) if rule == R.SGD else {}
         mine, ref = cls(_params(), **kw), R.torch_class(rule)(_params(), **kw)
-        assert isinstance(mine, AdamW) and mine.rule == rule == getattr(L, "OPT_" + R.NAMES[rule].upper())
+        assert isinstance(mine, ArenaOptimizer) and not isinstance(mine, AdamW) and mine.rule == rule == getattr(L, "OPT_" + R.NAMES[rule].upper())
         assert mine.defaults == ref.defaults
         a, b = mine.state_dict(), ref.state_dict()
         assert a["param_groups"] == b["param_groups"] and a["state"] == {} == b["state"]
@@ -323,9 +323,20 @@ def test_update_bytes_per_rule():
 def test_exchange_choice_and_attach():
     from vln_hamt_amd import _lib as L
     from vln_hamt_amd import parallel
-    from vln_hamt_amd.optim import AdamW, Ralamb, RangerLars
+    from vln_hamt_amd.optim import AdamW, ArenaOptimizer, Ralamb, RangerLars
     assert not parallel.per_tensor_update(AdamW(_params()))
     assert parallel.per_tensor_update(Ralamb(_params())) and parallel.per_tensor_update(RangerLars(_params()))
+    # the seven public classes: each an ArenaOptimizer, none a subclass of another rule's class but RangerLars(Ralamb); only AdamW's
+    # update has a range form, and every other class refuses attach() with its own reason
+    assert AdamW.owned_slice_update and AdamW.attach is not ArenaOptimizer.attach
+    for cls in (Ralamb, RangerLars, *_classes().values()):
+        o = cls(_params(), lr=0.1)
+        assert isinstance(o, ArenaOptimizer) and not isinstance(o, AdamW) and not o.owned_slice_update
+        assert isinstance(o, Ralamb) == (cls in (Ralamb, RangerLars))
+        reason = "trust ratio needs its whole norm" if isinstance(o, Ralamb) else "hamt_optim_table has no range form"
+        with pytest.raises(L.HamtError, match=f"{cls.__name__}: .*attach / overlap_update.*{reason}"):
+            o.attach(torch.nn.Linear(2, 2))
+    assert issubclass(AdamW, ArenaOptimizer)
     for rule, cls in _classes().items():
         o = cls(_params(), lr=0.1)
         assert parallel.per_tensor_update(o) and not o.owned_slice_update

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which parameters' gradients still arrive as autograd tensors and are copied into the gradient arena by optim.AdamW._pack_grads
+"""Which parameters' gradients still arrive as autograd tensors and are copied into the gradient arena by optim.ArenaOptimizer._pack_grads
 (everything else is written in place by its producer)?  One eager step per task at B = 64.  usage: packed_grads_probe.py [batch]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

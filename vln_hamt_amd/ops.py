@@ -179,7 +179,7 @@ def weight_operand(w: torch.Tensor, prec: str) -> torch.Tensor:
     wd = w.detach()
     if prec == "fp32":
         return wd
-    a = getattr(w, "_hamt_arena16", None)       # (bf16 view, fp32 arena, arena version, parameter version at last sync): optim.AdamW
+    a = getattr(w, "_hamt_arena16", None)       # (bf16 view, fp32 arena, arena version, parameter version at last sync): optim.ArenaOptimizer
     if a is not None and arena16_valid(w, a):
         return a[0]
     c = getattr(w, "_hamt_w16", None)
@@ -331,7 +331,7 @@ def _linear_bwd(dy2, x2, x16, weight, prec, need_dx, need_dw, need_db, dx_out=No
     slot_w = _accum_slot(weight) if (need_dw and not (K <= 8)) else None
     if slot_w is not None:
         # a parameter outside the grouped launch (the fp32 prediction heads) that owns a zero-at-the-start-of-a-step slot in the
-        # optimizer's gradient arena: ADD dW (and db) there -- no autograd tensor for optim.AdamW._pack_grads to copy in afterwards
+        # optimizer's gradient arena: ADD dW (and db) there -- no autograd tensor for optim.ArenaOptimizer._pack_grads to copy in afterwards
         from . import wgrad
         wgrad.queue(dy2.device).current()
         if fast:

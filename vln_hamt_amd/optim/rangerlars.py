@@ -1,10 +1,11 @@
 """RangerLars = Ralamb (RAdam with a LARS-style per-tensor trust ratio, pretrain_src/optim/ralamb.py) wrapped in Lookahead
-(lookahead.py; rangerlars.py:12-14), as HIP kernels over the flat fp32 arenas of optim.AdamW.
+(lookahead.py; rangerlars.py:12-14), as HIP kernels over the flat fp32 arenas of optim.arena.
 
 The arena machinery (re-homed parameters, bf16 shadow, gradient packing, the deferred global-norm clip, the static launch
-sequence that graph.GraphedTrainStep captures) is AdamW's; the update is three launches of ``hamt_ralamb_table``: moments and
-per-item partial sums of squares, the per-parameter trust ratio, the update with the Lookahead sync.  The host keeps:
-  * the AdamW table layout {lr, s*lr, weight_decay, active} (s: the RAdam step size, float64 like the reference's Python
+sequence that graph.GraphedTrainStep captures) is optim.arena.ArenaOptimizer's; the update is three launches of
+``hamt_ralamb_table``: moments and per-item partial sums of squares, the per-parameter trust ratio, the update with the Lookahead
+sync.  The host keeps:
+  * the arena's first table {lr, s*lr, weight_decay, active} (s: the RAdam step size, float64 like the reference's Python
     scalars) -- the gradient-norm kernels and parallel.py read its column 3;
   * a second table {N_sma >= 5, Lookahead action (0 none, 1 create, 2 interpolate), alpha, -weight_decay*lr};
   * a static item table (each item inside one parameter, at most 4096 elements, in arena order) with one partial slot per item;
@@ -19,18 +20,17 @@ other process can map back).
 from __future__ import annotations
 
 import math
-from typing import List, Optional
 
 import numpy as np
 import torch
-from torch.optim import Optimizer
 
 from .. import _lib as L
 from ..ops import _p, _stream
-from .adamw import AdamW
+from .arena import ArenaOptimizer, check_adam_args
 
 ITEM4 = 1024        # float4 per item (256 threads x 4): the kernels' chunk
 NONE, CREATE, INTERPOLATE = 0.0, 1.0, 2.0
+STAT_KEYS = ("weight_norm", "adam_norm", "trust_ratio")     # state keys of the columns of _stats
 
 
 def ralamb_coef(step: int, beta1: float, beta2: float):
@@ -57,23 +57,16 @@ def item_table(ends: np.ndarray, n: int) -> np.ndarray:
     return tab.astype(np.int32), nitems
 
 
-class Ralamb(AdamW):
+class Ralamb(ArenaOptimizer):
     """The reference's Ralamb (ralamb.py) on the arenas: RangerLars without the Lookahead wrapper."""
 
     _lookahead = False
-    owned_slice_update = False      # every parameter's trust ratio needs its whole norm
+    n_tables = 2                    # the arena's {lr, s*lr, weight_decay, active} and _rl
+    no_range_reason = "every parameter's trust ratio needs its whole norm first"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        if lr < 0.0:
-            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
-        if not 0.0 <= eps:
-            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
-        Optimizer.__init__(self, params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._init_host_state()
+        check_adam_args(lr, betas, eps)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._la_pending = None     # (actions, created) of the counted step: zero_grad() of a dropped pass takes them back
 
     # ---------------------------------------------------------------- arenas
@@ -85,31 +78,17 @@ class Ralamb(AdamW):
         self._items = torch.from_numpy(tab).to(dev)
         self._partials = torch.zeros(2 * self._nitems, dtype=torch.float32, device=dev)
         self._stats = torch.zeros(np_, 4, dtype=torch.float32, device=dev)     # {weight_norm, adam_norm, trust_ratio, 0}
-        # both tables in one device block (one H2D copy per step); _hyp keeps AdamW's [nparams, 4] layout
-        self._tables = torch.zeros(2, np_, 4, dtype=torch.float32, device=dev)
-        self._hyp, self._rl = self._tables[0], self._tables[1]
-        self._hyp_ring = [torch.zeros(2, np_, 4, dtype=torch.float32).pin_memory() for _ in range(4)]
-        self._hyp_events = [None] * 4
+        self._rl = self._tables[1]
         self._flat_slow = torch.zeros_like(self._flat_p) if self._lookahead else None
         self._has_slow = np.zeros(np_, dtype=bool)
 
-    def attach(self, model, chunk_elems: int = 8 << 20):
-        raise L.HamtError(f"{type(self).__name__}: the update cannot run chunk by chunk next to the next forward pass (attach / "
-                          "overlap_update): every parameter's trust ratio needs its whole norm first")
-
-    def update_bytes(self, active=None, sync=False) -> float:
-        """algorithmic HBM bytes of one update: pass 1 reads p, g, m, v and writes m, v (24 per element, + 4 where the gradient slot
-        is zeroed), pass 3 reads p, m, v and writes p and the bf16 shadow (18), + 8 (slow weights read and written) on a Lookahead
-        sync (`sync`)"""
-        self.materialize()
-        sizes = np.diff(np.concatenate([[0], self._ends.cpu().numpy()])).astype(np.float64)
-        per = sizes * (np.where(self._keep == 2.0, 42.0, 46.0) + (8.0 if sync and self._lookahead else 0.0))
-        if active is not None:
-            per = per * np.asarray(active, dtype=np.float64)
-        return float(per.sum())
+    def _bytes_per_element(self, sync=False):
+        """pass 1 reads p, g, m, v and writes m, v (24 per element), pass 3 reads p, m, v and writes p and the bf16 shadow (18),
+        + 8 (slow weights read and written) on a Lookahead sync (`sync`)"""
+        return 42.0 + (8.0 if sync and self._lookahead else 0.0)
 
     # ---------------------------------------------------------------- host part of a step
-    def _advance_lookahead(self, act: np.ndarray):
+    def _advanced(self, act: np.ndarray):
         """lookahead.py:48-52: every group's counter advances; at a multiple of k the parameters with a gradient sync"""
         actions = np.zeros(len(self._params), dtype=np.float32)
         if self._lookahead:
@@ -120,67 +99,31 @@ class Ralamb(AdamW):
                     actions[sel] = np.where(self._has_slow[sel], INTERPOLATE, CREATE)
         created = actions == CREATE
         self._has_slow |= created
-        return actions, created
+        self._la_pending = actions, created
 
-    def host_table(self, active: Optional[List[bool]] = None, advance: bool = True) -> np.ndarray:
-        """AdamW.host_table's contract; the result is [2, nparams, 4]: the AdamW-layout table {lr, s*lr, weight_decay, active} and
-        the RangerLars table {N_sma >= 5, Lookahead action, alpha, -weight_decay*lr}."""
-        self.materialize()
-        flags = self.table_flags(active)
-        act = flags != 0
-        if advance:
-            self._steps[act] += 1
-            self._counted = act.copy()
-            self._la_pending = self._advance_lookahead(act)
+    def _fill_table(self, h, t, lr, wd):
+        """column 1 of the first table: s*lr; the RangerLars table {N_sma >= 5, Lookahead action, alpha, -weight_decay*lr}"""
         actions = self._la_pending[0] if self._la_pending is not None else np.zeros(len(self._params), dtype=np.float32)
         b1, b2 = self.param_groups[0]["betas"]
-        coefs = {t: ralamb_coef(t, b1, b2) for t in set(np.maximum(self._steps, 1).tolist())}
-        rect = np.array([coefs[max(int(t), 1)][0] for t in self._steps], dtype=np.float32)
-        s = np.array([coefs[max(int(t), 1)][1] for t in self._steps], dtype=np.float64)
-        lr = np.array([g["lr"] for g in self.param_groups], dtype=np.float64)[self._gidx_np]
-        wd = np.array([g["weight_decay"] for g in self.param_groups], dtype=np.float64)[self._gidx_np]
+        coefs = {k: ralamb_coef(k, b1, b2) for k in set(t.astype(np.int64).tolist())}
+        rect = np.array([coefs[int(k)][0] for k in t], dtype=np.float32)
+        s = np.array([coefs[int(k)][1] for k in t], dtype=np.float64)
         alpha = np.array([g.get("lookahead_alpha", 0.0) for g in self.param_groups], dtype=np.float64)[self._gidx_np]
-        h = np.zeros((2, len(self._params), 4), dtype=np.float32)
-        h[0, :, 0], h[0, :, 1], h[0, :, 2], h[0, :, 3] = lr, s * lr, wd, flags
+        h[0, :, 1] = s * lr
         h[1, :, 0], h[1, :, 1], h[1, :, 2], h[1, :, 3] = rect, actions, alpha, -wd * lr
-        self._table_active = flags
-        return h
 
-    def upload_table(self, table: Optional[np.ndarray]):
-        """both device tables in one async copy from the pinned ring (None: nothing active, the launches touch nothing)"""
-        self.materialize()
-        k = self._hyp_slot
-        self._hyp_slot = (k + 1) % len(self._hyp_ring)
-        if self._hyp_events[k] is not None:
-            self._hyp_events[k].synchronize()
-        h = self._hyp_ring[k].numpy()
-        if table is None:
-            h[:] = 0.0
-        else:
-            h[:] = table
-        self._tables.copy_(self._hyp_ring[k], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._hyp_events[k] = ev
-
-    def launch_step(self, zero_grad_arena: bool = True):
-        """Device side of a step: hamt_ralamb_table's three launches (static; capturable)."""
+    def _launch(self, gn, max_norm, zero_grad_arena):
+        """hamt_ralamb_table's three launches"""
         g0 = self.param_groups[0]
         b1, b2 = g0["betas"]
-        gn, max_norm = self._pending_clip if self._pending_clip is not None else (None, 0.0)
-        self._counted = None
-        if zero_grad_arena:
-            self._flat_g._hamt_dirty = False
         slow = self._flat_slow
         L.check(L.load().hamt_ralamb_table(_p(self._flat_p), _p(self._flat_g), _p(self._flat_m), _p(self._flat_v), _p(self._flat_p16),
                                            _p(slow) if slow is not None else None, _p(self._items), self._nitems, _p(self._hyp),
-                                           _p(self._rl), len(self._params), _p(self._partials), _p(self._stats), _p(gn), float(max_norm),
-                                           b1, b2, 1 - b1, 1 - b2, g0["eps"], int(zero_grad_arena), _stream()), "hamt_ralamb_table")
+                                           _p(self._rl), len(self._params), _p(self._partials), _p(self._stats), gn, max_norm,
+                                           b1, b2, 1 - b1, 1 - b2, g0["eps"], zero_grad_arena, _stream()), "hamt_ralamb_table")
 
-    def zero_grad(self, set_to_none: bool = True):
-        counted = self._built and self._counted is not None
-        super().zero_grad(set_to_none=set_to_none)
-        if counted and self._la_pending is not None:
+    def _taken_back(self):
+        if self._la_pending is not None:
             # the dropped pass was counted: take its Lookahead step back as well (the reference counts inside step() only)
             actions, created = self._la_pending
             if self._lookahead:
@@ -202,22 +145,7 @@ class Ralamb(AdamW):
     def state_dict(self):
         """Ralamb's per-parameter state {'step', 'exp_avg', 'exp_avg_sq', 'weight_norm', 'adam_norm', 'trust_ratio'} (ralamb.py:39-41,
         88-90) + param_groups; RangerLars adds 'slow_state' {index: {'slow_buffer'}} (lookahead.py:54-66, keyed by index)."""
-        if not self._built:
-            sd = Optimizer.state_dict(self)
-        else:
-            self.wait_update()
-            stats = self._stats.clone()
-            self.state.clear()
-            for i, (p, o) in enumerate(zip(self._params, self._offs)):
-                if self._steps[i] > 0:
-                    n = p.numel()
-                    self.state[p] = {"step": int(self._steps[i]), "exp_avg": self._flat_m[o:o + n].view(p.shape).clone(),
-                                     "exp_avg_sq": self._flat_v[o:o + n].view(p.shape).clone(), "weight_norm": stats[i, 0].clone(),
-                                     "adam_norm": stats[i, 1].clone(), "trust_ratio": stats[i, 2].clone()}
-            try:
-                sd = Optimizer.state_dict(self)
-            finally:
-                self.state.clear()
+        sd = super().state_dict()
         if not self._lookahead:
             return sd
         slow = {}
@@ -228,35 +156,38 @@ class Ralamb(AdamW):
                     slow[tidx[id(p)]] = {"slow_buffer": self._flat_slow[o:o + p.numel()].view(p.shape).clone()}
         return {"state": sd["state"], "slow_state": slow, "param_groups": sd["param_groups"]}
 
-    @torch.no_grad()
-    def load_state_dict(self, state_dict):
-        """Restore moments, step counts, norms and (RangerLars) the slow weights; a dict without 'slow_state' starts the slow weights
-        fresh, as the reference does (lookahead.py:75-80)."""
-        Optimizer.load_state_dict(self, {"state": state_dict["state"], "param_groups": state_dict["param_groups"]})
+    def _state_of(self, i, p, o):
+        st = super()._state_of(i, p, o)
+        for c, key in enumerate(STAT_KEYS):
+            st[key] = self._stats[i, c].clone()
+        return st
+
+    def _groups_loaded(self):
         if self._lookahead:
             for name, default in self.defaults.items():
                 for g in self.param_groups:
                     g.setdefault(name, default)
-        self.materialize()
-        self.wait_update()
-        self._flat_m.zero_()
-        self._flat_v.zero_()
+
+    def _reset_state(self):
+        super()._reset_state()
         self._stats.zero_()
-        self._steps[:] = 0
-        for i, (p, o) in enumerate(zip(self._params, self._offs)):
-            st = self.state.get(p)
-            if st:
-                n = p.numel()
-                self._flat_m[o:o + n].copy_(st["exp_avg"].reshape(-1))
-                self._flat_v[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
-                self._steps[i] = int(st["step"])
-                for c, key in enumerate(("weight_norm", "adam_norm", "trust_ratio")):
-                    if key in st:
-                        self._stats[i, c] = torch.as_tensor(st[key], dtype=torch.float32)
-        self.state.clear()
         self._has_slow[:] = False
+        self._la_pending = None
         if self._lookahead:
             self._flat_slow.zero_()
+
+    def _restore(self, i, p, o, st):
+        super()._restore(i, p, o, st)
+        for c, key in enumerate(STAT_KEYS):
+            if key in st:
+                self._stats[i, c] = torch.as_tensor(st[key], dtype=torch.float32)
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict):
+        """Restore moments, step counts, norms and (RangerLars) the slow weights; a dict without 'slow_state' starts the slow weights
+        fresh, as the reference does (lookahead.py:75-80)."""
+        super().load_state_dict({"state": state_dict["state"], "param_groups": state_dict["param_groups"]})
+        if self._lookahead:
             slow = state_dict.get("slow_state") or {}
             arena_of = {t: self._index_of[pid] for pid, t in self._torch_index().items()}
             for k, ent in slow.items():
@@ -268,9 +199,6 @@ class Ralamb(AdamW):
                     o, p = self._offs[i], self._params[i]
                     self._flat_slow[o:o + p.numel()].copy_(ent["slow_buffer"].reshape(-1))
                     self._has_slow[i] = True
-        self._counted = None
-        self._la_pending = None
-        self.refresh_shadow()
 
 
 class RangerLars(Ralamb):

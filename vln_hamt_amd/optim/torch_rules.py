@@ -1,14 +1,15 @@
 """torch.optim's AdamW / Adam / RMSprop / SGD -- the four choices of the finetune agents' ``--optim`` (finetune_src/r2r/agent_cmt.py:62-77;
-every finetune recipe runs ``adamW``) -- as one HIP launch over the flat fp32 arenas of optim.AdamW.
+every finetune recipe runs ``adamW``) -- as one HIP launch over the flat fp32 arenas of optim.arena.
 
 The arena machinery (re-homed parameters, bf16 shadow, gradient packing, the deferred global-norm clip, the pinned table ring, the
-prepare_step / launch_step contract that graph.GraphedTrainStep captures) is optim.AdamW's; the update is ``hamt_optim_table`` with the
-rule as its first argument.  torch's rules are not the pretraining AdamW's (optim/adamw.py of the reference, HF style) with other
-hyper-parameters: torch decays BEFORE the update and on every parameter, and adds eps AFTER dividing sqrt(v) by sqrt(1 - beta2^t).
+prepare_step / launch_step contract that graph.GraphedTrainStep captures) is optim.arena.ArenaOptimizer's; the update is
+``hamt_optim_table`` with the rule as its first argument.  torch's rules are not the pretraining AdamW's (optim/adamw.py of the reference,
+HF style) with other hyper-parameters: torch decays BEFORE the update and on every parameter, and adds eps AFTER dividing sqrt(v) by
+sqrt(1 - beta2^t).
 
 The host keeps two [nparams, 4] tables in one device block (one H2D copy per step), every entry formed in float64 and rounded once, as
 torch does with its Python scalars:
-  * hyp {lr, lr / (1 - beta1^t), weight_decay, active}: optim.AdamW's layout (the gradient-norm kernels and parallel.py read column 3);
+  * hyp {lr, lr / (1 - beta1^t), weight_decay, active}: the arena's first table (the gradient-norm kernels and parallel.py read column 3);
   * aux {1 / sqrt(1 - beta2^t), 1 - lr * weight_decay, 0, 0}.
 t is the parameter's own step count; it advances only where there is a gradient, as torch's does.  A rule's unused moment arenas are
 not allocated (RMSprop: no exp_avg; SGD: neither).  ``state_dict()`` / ``load_state_dict()`` speak torch's layout, so a checkpoint moves
@@ -16,15 +17,12 @@ between these classes and torch.optim in both directions (``--resume_optimizer``
 """
 from __future__ import annotations
 
-from typing import List, Optional
-
 import numpy as np
 import torch
-from torch.optim import Optimizer
 
 from .. import _lib as L
 from ..ops import _p, _stream
-from .adamw import AdamW
+from .arena import ArenaOptimizer
 
 
 def _refuse(name: str, **options):
@@ -34,17 +32,17 @@ def _refuse(name: str, **options):
             raise ValueError(f"{name}: {k}={v!r} is not implemented by hamt_optim_table (only {k}={default!r})")
 
 
-class _TorchRule(AdamW):
+class _TorchRule(ArenaOptimizer):
     rule = None                     # hamt_opt_rule
     torch_class = None              # its defaults (and its checks of lr / betas / eps / weight_decay) are taken from the installed torch
     moment_keys = ()                # torch's state keys of the m / v arenas this rule owns
-    owned_slice_update = False      # there is no range form of hamt_optim_table: attach() refuses, parallel.py takes the all-reduce exchange
+    n_tables = 2                    # hyp and _aux
+    no_range_reason = "hamt_optim_table has no range form"      # (attach() refuses, parallel.py takes the all-reduce exchange)
 
     def _init(self, params, **given):
         params = list(params)
         defaults = dict(self.torch_class([torch.nn.Parameter(torch.zeros(1))], **given).defaults)    # raises torch's own ValueErrors
-        Optimizer.__init__(self, params, defaults)
-        self._init_host_state()
+        super().__init__(params, defaults)
 
     # ---------------------------------------------------------------- arenas
     def _check_groups(self):
@@ -63,33 +61,14 @@ class _TorchRule(AdamW):
         b1, b2 = g["betas"]
         return float(b1), float(b2), float(g["eps"])
 
-    def _alloc_moments(self):
-        self._flat_m = torch.zeros_like(self._flat_p) if len(self.moment_keys) == 2 else None      # exp_avg
-        self._flat_v = torch.zeros_like(self._flat_p) if len(self.moment_keys) >= 1 else None      # exp_avg_sq / square_avg
-
     def _build(self):
         super()._build()
-        np_, dev = len(self._params), self._flat_p.device
-        self._tables = torch.zeros(2, np_, 4, dtype=torch.float32, device=dev)
-        self._hyp, self._aux = self._tables[0], self._tables[1]
-        self._table_dev = self._tables
-        self._hyp_ring = [torch.zeros(2, np_, 4, dtype=torch.float32).pin_memory() for _ in range(4)]
-        self._hyp_events = [None] * 4
+        self._aux = self._tables[1]
 
-    def attach(self, model, chunk_elems: int = 8 << 20):
-        raise L.HamtError(f"{type(self).__name__}: the update cannot run chunk by chunk next to the next forward pass (attach / "
-                          "overlap_update): hamt_optim_table has no range form")
-
-    def update_bytes(self, active=None, moments=None) -> float:
-        """algorithmic HBM bytes of one update: p and g read, p and the bf16 shadow written (14 per element), 8 more per moment arena
-        the rule owns (`moments`: of another rule over the same arena), + 4 where the gradient slot is zeroed: 34 / 34 / 26 / 18 for
-        AdamW / Adam / RMSprop / SGD"""
-        self.materialize()
-        sizes = np.diff(np.concatenate([[0], self._ends.cpu().numpy()])).astype(np.float64)
-        per = sizes * (14.0 + 8.0 * (len(self.moment_keys) if moments is None else moments) + np.where(self._keep == 2.0, 0.0, 4.0))
-        if active is not None:
-            per = per * np.asarray(active, dtype=np.float64)
-        return float(per.sum())
+    def _bytes_per_element(self, moments=None):
+        """p and g read, p and the bf16 shadow written (14 per element), 8 more per moment arena the rule owns (`moments`: of another
+        rule over the same arena): with the 4 of a zeroed gradient slot 34 / 34 / 26 / 18 for AdamW / Adam / RMSprop / SGD"""
+        return 14.0 + 8.0 * (len(self.moment_keys) if moments is None else moments)
 
     # ---------------------------------------------------------------- host part of a step
     def _columns(self, t, lr, wd):
@@ -101,83 +80,32 @@ class _TorchRule(AdamW):
         b1, b2 = (float(np.float32(b)) for b in self._launch_scalars(self.param_groups[0])[:2])
         return lr / (1.0 - b1 ** t), 1.0 / np.sqrt(1.0 - b2 ** t), 1.0 - lr * wd
 
-    def host_table(self, active: Optional[List[bool]] = None, advance: bool = True) -> np.ndarray:
-        """AdamW.host_table's contract; the result is [2, nparams, 4]: hyp and aux (see the module's docstring)."""
-        self.materialize()
-        flags = self.table_flags(active)
-        act = flags != 0
-        if advance:
-            self._steps[act] += 1
-            self._counted = act.copy()
-        t = np.maximum(self._steps, 1).astype(np.float64)
-        lr = np.array([g["lr"] for g in self.param_groups], dtype=np.float64)[self._gidx_np]
-        wd = np.array([g["weight_decay"] for g in self.param_groups], dtype=np.float64)[self._gidx_np]
-        h = np.zeros((2, len(self._params), 4), dtype=np.float32)
-        h[0, :, 0], h[0, :, 2], h[0, :, 3] = lr, wd, flags
+    def _fill_table(self, h, t, lr, wd):
         h[0, :, 1], h[1, :, 0], h[1, :, 1] = self._columns(t, lr, wd)
-        self._table_active = flags
-        return h
 
-    def launch_step(self, zero_grad_arena: bool = True):
-        """Device side of a step: one hamt_optim_table launch (static; capturable)."""
+    def _launch(self, gn, max_norm, zero_grad_arena):
         b1, b2, eps = self._launch_scalars(self.param_groups[0])
-        gn, max_norm = self._pending_clip if self._pending_clip is not None else (None, 0.0)
-        self._counted = None
-        if zero_grad_arena:
-            self._flat_g._hamt_dirty = False
         L.check(L.load().hamt_optim_table(self.rule, self._n, _p(self._flat_p), _p(self._flat_g), _p(self._flat_m), _p(self._flat_v),
-                                          _p(self._flat_p16), _p(self._ends), _p(self._hyp), _p(self._aux), len(self._params), _p(gn),
-                                          float(max_norm), b1, b2, eps, int(zero_grad_arena), _stream()), "hamt_optim_table")
+                                          _p(self._flat_p16), _p(self._ends), _p(self._hyp), _p(self._aux), len(self._params), gn,
+                                          max_norm, b1, b2, eps, zero_grad_arena, _stream()), "hamt_optim_table")
 
     # ---------------------------------------------------------------- checkpointing (agent_cmt.py:607-644 saves optimizer.state_dict())
-    def _arenas(self):
-        return [a for a in (self._flat_m, self._flat_v) if a is not None]
-
-    def state_dict(self):
-        """torch's layout: per stepped parameter {'step' (0-dim float32 CPU tensor), the rule's moments under torch's names}, plus
-        param_groups with torch's keys."""
-        if not self._built:
-            return Optimizer.state_dict(self)
-        self.wait_update()
-        self.state.clear()
-        for i, (p, o) in enumerate(zip(self._params, self._offs)):
-            if self._steps[i] > 0:
-                self.state[p] = self._state_of(i, p, o)
-        try:
-            return Optimizer.state_dict(self)
-        finally:
-            self.state.clear()
-
     def _state_of(self, i, p, o):
-        st = {"step": torch.tensor(float(self._steps[i]), dtype=torch.float32)}
-        for key, a in zip(self.moment_keys, self._arenas()):
-            st[key] = a[o:o + p.numel()].view(p.shape).clone()
+        """torch's layout: {'step' (0-dim float32 CPU tensor), the rule's moments under torch's names}"""
+        st = super()._state_of(i, p, o)
+        st["step"] = torch.tensor(float(self._steps[i]), dtype=torch.float32)
         return st
 
-    @torch.no_grad()
-    def load_state_dict(self, state_dict):
-        """Restore moments and per-parameter step counts from torch's layout ('step' a tensor or, as older torch wrote it, an int)."""
-        Optimizer.load_state_dict(self, state_dict)
+    def _groups_loaded(self):
         for name, default in self.defaults.items():          # (a checkpoint of another torch version may lack newer keys)
             for g in self.param_groups:
                 g.setdefault(name, default)
         self.materialize()
         self._check_groups()
-        self.wait_update()
-        for a in self._arenas():
-            a.zero_()
-        self._steps[:] = 0
-        for i, (p, o) in enumerate(zip(self._params, self._offs)):
-            st = self.state.get(p)
-            if st:
-                for key, a in zip(self.moment_keys, self._arenas()):
-                    a[o:o + p.numel()].copy_(st[key].reshape(-1))
-                if "step" in st:
-                    self._steps[i] = int(round(float(st["step"])))
-        self.state.clear()
-        self._counted = None
-        self._table_ready = False
-        self.refresh_shadow()
+
+    def _restore(self, i, p, o, st):
+        """'step' is a tensor or, as older torch wrote it, an int; a stepped parameter of SGD has none"""
+        super()._restore(i, p, o, dict(st, step=round(float(st.get("step", 0)))))
 
 
 class TorchAdamW(_TorchRule):

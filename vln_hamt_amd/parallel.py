@@ -3,7 +3,7 @@
 The HAMT path shards by *samples* only: every rank runs the same task on its own minibatch and
 the only exchange is the gradient average.  The reference gets it from torch DDP (pretrain_src/utils/misc.py:52-65,
 find_unused_parameters=True because each proxy task leaves the other tasks' heads without gradient).  Here the
-gradients already sit in ONE flat fp32 arena (optim.AdamW; the GEMM weight gradients are written there directly by
+gradients already sit in ONE flat fp32 arena (optim.ArenaOptimizer; the GEMM weight gradients are written there directly by
 the grouped end-of-pass launch, wgrad.py, which bypasses the per-parameter autograd hooks DDP relies on), so the
 exchange is a few large RCCL all-reduces over that arena (`allreduce_grads`): ring collectives over xGMI are per-link
 bound, and 128 MiB messages run at the link rate without per-bucket bookkeeping or unused-parameter detection.
@@ -156,7 +156,7 @@ def allreduce_grads(optimizer, wire: str | None = None) -> None:
     (the grouped weight gradients are already there) and all-reduce the arena.  Call between backward and clip/step."""
     if not optimizer._packed:
         optimizer._pack_grads()
-    # the per-tile sums of squares the weight-gradient launch left (optim.AdamW.note_fused_sumsq) describe THIS rank's gradients
+    # the per-tile sums of squares the weight-gradient launch left (optim.ArenaOptimizer.note_fused_sumsq) describe THIS rank's gradients
     # before the average; the collective rewrites the arena through raw pointers, which no version counter sees
     optimizer.clear_fused_sumsq()
     allreduce_mean_(optimizer._flat_g, wire=wire or default_wire("fp32"))
@@ -354,7 +354,7 @@ def range_finality(static_ranges, plan_ranges):
 
 
 def shardable(optimizer, world: int) -> bool:
-    """Can the arenas be split into 8-element granules over `world` ranks?  (Region ends are multiples of optim.adamw.REGION_ALIGN =
+    """Can the arenas be split into 8-element granules over `world` ranks?  (Region ends are multiples of optim.arena.REGION_ALIGN =
     512 elements: true whenever 8 * world divides 512, i.e. world in {1, 2, 4, 8, 16, 32, 64}.)"""
     o = optimizer.materialize()
     return o._n % (8 * world) == 0 and o._n_shadow_only % (8 * world) == 0
@@ -442,10 +442,10 @@ class ShardedGradSync(OverlappedGradSync):
 
     def attach_gather(self, model: torch.nn.Module):
         """Gate `model`'s next forward pass range by range behind the parameters' all-gathers of update() instead of making the
-        stream wait for all of them: forward pre-hooks on every module (optim.adamw._Overlap: the machinery of AdamW.attach, with
+        stream wait for all of them: forward pre-hooks on every module (optim.arena._Overlap: the machinery of AdamW.attach, with
         the static exchange ranges as its chunks and the communication stream as its stream).  Eager loops only; under graph replay
         the all-gathers sit between the replays on the launching stream, as before."""
-        from .optim.adamw import _Overlap
+        from .optim.arena import _Overlap
         o = self.opt
         self.detach_gather()
         n_a = o._n_shadow_only
@@ -597,7 +597,7 @@ class ShardedGradSync(OverlappedGradSync):
         return out
 
     def _launch_sumsq(self):
-        """sum of squares of the owned gradient chunks -> self._gsq (active parameters only: see optim.AdamW._keep)"""
+        """sum of squares of the owned gradient chunks -> self._gsq (active parameters only: see optim.ArenaOptimizer._keep)"""
         from . import _lib as L
         from .ops import _p, _stream
         o, lib = self.opt, L.load()
@@ -671,7 +671,7 @@ class ShardedGradSync(OverlappedGradSync):
             # eager loop (parallel.ArenaDataParallel): the parameters' all-gathers run on the communication stream in the order a forward
             # pass reads them -- the fp32-read region (embedding tables, biases, LayerNorm: the first kernels), then the GEMM-weight
             # ranges in arena (= registration = use) order -- one event per range; the NEXT forward starts right away and every module
-            # waits for the range(s) that hold its parameters (attach_gather: optim.AdamW's pre-hook gates), instead of the whole
+            # waits for the range(s) that hold its parameters (attach_gather: optim.arena._Overlap's pre-hook gates), instead of the whole
             # forward waiting for ~350 MB of all-gather at world 8 (DDP overlaps the same way: utils/misc.py:57-58 + main_r2r.py:246)
             cur = torch.cuda.current_stream()
             self.comm.wait_stream(cur)
@@ -692,7 +692,7 @@ class ShardedGradSync(OverlappedGradSync):
                     self._all_gather_inplace(o._flat_p[lo:hi])
             if o._n > n_a:                                                # bf16 images of the >= 2-D fp32-read parameters (tied MLM decoder ...)
                 L.check(lib.hamt_cast_f32_bf16(o._n - n_a, _p(o._flat_p[n_a:]), _p(o._flat_p16[n_a:]), _stream()), "hamt_cast_f32_bf16")
-        o._counted = None                                             # the counted step is applied (optim.AdamW.zero_grad)
+        o._counted = None                                             # the counted step is applied (optim.ArenaOptimizer.zero_grad)
         o.mark_updated()
         self._unconsumed = False
         o._shard_stale = self.world > 1
@@ -738,7 +738,7 @@ class ArenaDataParallel(torch.nn.Module):
       * parameters without a gradient this step (the other tasks' heads) are exchanged as zeros and skipped by the update:
         find_unused_parameters=True semantics;
       * with the sharded exchange, `clip_grad_norm_` returns the global norm from the owned chunks + one 4-byte all-reduce, and
-        `optimizer.step()` runs the owned-slice AdamW and the parameter all-gathers (optim.AdamW.step sees `_sharded_sync`).
+        `optimizer.step()` runs the owned-slice AdamW and the parameter all-gathers (optim.ArenaOptimizer.step sees `_sharded_sync`).
 
     `.module` is the wrapped model (utils/save.py:36 `model.module if hasattr(model, 'module') else model`)."""
 

@@ -8,7 +8,7 @@ once, when the autograd engine finishes the pass (``queue_callback``): one chip-
 full-length K loops, bias sums fused in (one extra MFMA per fragment), no split-K scratch and no reduce pass.
 
 Where the result goes: a parameter that owns a slot in the optimizer's flat gradient arena (``_hamt_grad_slot``,
-set by optim.AdamW) gets its gradient written there directly and ``p.grad`` becomes that view, so the optimizer has
+set by optim.ArenaOptimizer) gets its gradient written there directly and ``p.grad`` becomes that view, so the optimizer has
 nothing to pack; otherwise a fresh fp32 tensor.  A parameter that already has a ``.grad`` when the queue is flushed
 (several uses in one pass, the embedding table tied to the MLM decoder, or gradient accumulation over passes) is
 accumulated into in place -- the sum autograd's AccumulateGrad would have formed.
@@ -183,7 +183,7 @@ def defer_ln_reduce(ws, red, M, H, want_dxsum, pairs):
 
 def mark_arena_dirty(slot: torch.Tensor):
     """A producer relied on `slot` (a view of the optimizer's flat gradient arena) being zero before it added into it: the arena
-    must be re-zeroed before the next pass even if no optimizer step runs in between (optim.AdamW.zero_grad checks the mark;
+    must be re-zeroed before the next pass even if no optimizer step runs in between (optim.ArenaOptimizer.zero_grad checks the mark;
     the update kernel zeroes the arena itself)."""
     base = slot._base if slot._base is not None else slot
     base._hamt_dirty = True
@@ -361,7 +361,7 @@ def _launch_items(ps: _Pass, items, later=frozenset()):
     lib = L.load()
     # Sum of squares of the gradients while their tiles are still in registers (hamt_wgrad_desc.ss): for every weight whose
     # gradient is STORED once in this pass straight into its gradient-arena slot -- the bulk of the parameters -- so that the
-    # global-norm clip does not have to read them back (optim.AdamW.global_grad_sumsq adds the slots' total to the table norm).
+    # global-norm clip does not have to read them back (optim.ArenaOptimizer.global_grad_sumsq adds the slots' total to the table norm).
     fused, ss_all, opt = [], None, None
     if not ps.cleared:
         ps.cleared = True
