@@ -33,7 +33,7 @@ extern "C" {
 
 #define HAMT_ABI_VERSION 2   /* 2 (round 6): hamt_gemm_ln_fwd / hamt_graph_split_* removed (round 5); hamt_embed_sum_bwd takes V and ws_bytes,
                               * hamt_scatter_add_rows_ordered takes T; hamt_wgrad_grouped_ex and the dtype HAMT_F16 added.  Entry points added since (the
-                              * policy / nav / obs / eval families, hamt_attn_cls_fwd, hamt_image_resample) change no existing signature and leave the number at 2. */
+                              * policy / nav / obs / eval families, hamt_attn_cls_fwd, hamt_image_resample, hamt_range_audit) change no existing signature and leave the number at 2. */
 
 typedef enum { HAMT_OK = 0, HAMT_ERR_ARG = -1, HAMT_ERR_UNSUPPORTED = -2, HAMT_ERR_LAUNCH = -3 } hamt_status;
 typedef enum { HAMT_F32 = 0, HAMT_BF16 = 1,
@@ -45,7 +45,10 @@ typedef enum { HAMT_F32 = 0, HAMT_BF16 = 1,
                /* IEEE half, for `C` of hamt_gemm (epilogue: none / HAMT_EPI_BIAS / HAMT_EPI_ACCUM) and for `x` / `z` of the LayerNorm family only: the output of a dense layer in front of a
                 * LayerNorm (vilmodel.py:139-143, 181-185) kept in two bytes with 10 mantissa bits instead of bf16's 7 -- the rounding of
                 * that interface is 8 x finer at the same HBM bytes (round 6: the bf16 head outputs at B = 64 drop from 1.03e-2 to
-                * ~6.5e-3 of the fp32 reference; dense outputs are O(1 .. 100), far inside half's range) */
+                * ~6.5e-3 of the fp32 reference).  The store clamps at +-65504 instead of writing inf.  With the random weights of the tests
+                * and the benchmark the dense outputs are O(1 .. 100), far inside half's range; a trained checkpoint with outlier channels
+                * need not be, and a clamped value is a silently wrong LayerNorm row -- hamt_range_audit counts the elements at the limit
+                * per dense layer, and the Python side (audit.HalfRangeWatch) reports them and moves single layers to HAMT_F32 outputs */
                HAMT_F16 = 3 } hamt_dtype;
 /* arithmetic of the contraction: bf16 MFMA operands with fp32 accumulate, or exact fp32 MFMA */
 typedef enum { HAMT_PREC_BF16 = 0, HAMT_PREC_F32 = 1 } hamt_prec;
@@ -854,6 +857,22 @@ int hamt_clip_scale(size_t n, float* g, const float* gnorm_sq, float max_norm, v
 
 /* rng[1] += 1 on the stream (new dropout epoch; call once per optimisation step) */
 int hamt_rng_advance(uint64_t* rng, void* stream);
+
+/* Range watch on a dense output (csrc/audit.hip): one pass over x [M, N] (row stride ld elements, ld >= N; dtype HAMT_F16, HAMT_BF16 or
+ * HAMT_F32) folded into rec, four int64 values in DEVICE memory that the call ADDS to / maximises -- nothing is read back, a caller
+ * copies the record out when it wants to look:
+ *   rec[0] += elements at half's limit, |x| == 65504 (bits 0x7BFF under the sign); HAMT_F16 only, the other dtypes add 0.  The half store
+ *             clamps at +-65504, so every overflow arrives as exactly this value.  A result that legitimately rounds to 65504 is counted
+ *             too: the count bounds the clamps from above, and 0 proves there were none.
+ *   rec[1] += non-finite elements (exponent field all ones)
+ *   rec[2]  = max(rec[2], float32 bit pattern of the largest finite |x|), widened exactly from half / bf16 (non-negative float
+ *             patterns order like integers; a record starts at 0)
+ *   rec[3] += 1 (calls; M == 0 still counts, and reads nothing)
+ * Only the M x N elements named are read: 16 bytes per lane where x and ld * elementsize are 16-byte aligned (a contiguous x counts as
+ * one long row), element by element otherwise and for the N % (16 / elementsize) end of a row.  One launch, grid-stride over at most
+ * 1024 workgroups; integer atomics only (at most one per field per workgroup, none for a zero contribution), so the record does not
+ * depend on scheduling; no scratch.  Null pointers, another dtype, M < 0, N <= 0 or ld < N: HAMT_ERR_ARG, nothing is launched. */
+int hamt_range_audit(const void* x, int dtype, int M, int N, int64_t ld, int64_t* rec, void* stream);
 
 
 #ifdef __cplusplus

@@ -197,6 +197,7 @@ SIGNATURES = {
     "hamt_optim_table": [i32, sz, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_clip_scale": [sz, vp, vp, f32, vp],
     "hamt_rng_advance": [vp, vp],
+    "hamt_range_audit": [vp, i32, i32, i32, C.c_int64, vp, vp],
 }
 
 _lib = None

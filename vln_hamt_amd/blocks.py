@@ -26,6 +26,7 @@ import os
 import torch
 
 from . import _lib as L
+from . import audit
 from . import ops
 from . import wgrad
 from .ops import _ln_bwd, _ln_fwd, _p, _rup, _stream, cast_pad16, colsum, gemm, next_call_id, rng_state, shadow16, weight_operand
@@ -42,6 +43,12 @@ NO_SHADOW = os.environ.get("HAMT_NO_SHADOW") is not None
 # outputs give at + 4 bytes per element: HAMT_DENSE_OUT_F32=1).  HAMT_DENSE_OUT_BF16=1: bf16 as before (what a linear returns under autocast)
 O_DTYPE = (torch.float32 if os.environ.get("HAMT_DENSE_OUT_F32") == "1" else
            (torch.bfloat16 if os.environ.get("HAMT_DENSE_OUT_BF16") == "1" else torch.float16))
+
+
+def _o_dtype(w):
+    """O_DTYPE, or fp32 for a dense layer whose weight `w` audit.HalfRangeWatch.promote() marked: the GEMM and the LayerNorm take fp32
+    there already, and no backward reads `o` (it is in none of the three save_for_backward lists; `z` stays fp32 behind an fp32 `o`)"""
+    return torch.float32 if getattr(w, audit.PROMOTED_ATTR, False) else O_DTYPE
 
 
 # the saved gelu' image of the FFN blocks: one byte per element (hamt.h HAMT_U8G: 0.005 q - 0.13, |error| <= 0.0025 -- what bf16's rounding
@@ -196,8 +203,9 @@ class SelfAttnBlockFn(torch.autograd.Function):
         else:
             L.check(L.load().hamt_attn_small_fwd(C.byref(d), _p(q), _p(k), _p(v), _p(mask2), _p(ctx16), _p(lse), _p(rng), _stream()),
                     "hamt_attn_small_fwd")
-        o = torch.empty(M, H, dtype=O_DTYPE, device=dev)      # bf16: what a linear returns under autocast (ops._ln_fwd reads it as such)
+        o = torch.empty(M, H, dtype=_o_dtype(wo), device=dev)      # bf16: what a linear returns under autocast (ops._ln_fwd reads it as such)
         gemm(ctx16[:M], weight_operand(wo, "bf16"), o, bias=bo.detach())
+        if audit.ACTIVE is not None: ops.range_audit(o, audit.ACTIVE.row(wo))
         y, y16, z, mean, rstd, cid_ln = _ln_fwd(o, x2, gamma.detach(), beta.detach(), eps, p_hidden, 0.0, True)
         ctx.save_for_backward(x16, qkv16, ctx16, lse, mask2, z, mean, rstd, wq, bq, wk, bk, wv, bv, wo, bo, gamma)
         ctx.ln_params = (gamma, beta, bo)          # their gradients come from the LayerNorm-backward partials (ops._ln_bwd)
@@ -308,8 +316,9 @@ class CrossAttnBlockFn(torch.autograd.Function):
         else:
             L.check(L.load().hamt_attn_small_fwd(C.byref(d), _p(q16), _p(kv16[:, :H]), _p(kv16[:, H:]), _p(mask2), _p(ctx16), _p(lse),
                                                  _p(rng_state(dev)), _stream()), "hamt_attn_small_fwd")
-        o = torch.empty(Mq, H, dtype=O_DTYPE, device=dev)
+        o = torch.empty(Mq, H, dtype=_o_dtype(wo), device=dev)
         gemm(ctx16[:Mq], weight_operand(wo, "bf16"), o, bias=bo.detach())
+        if audit.ACTIVE is not None: ops.range_audit(o, audit.ACTIVE.row(wo))
         y, y16, z, mean, rstd, cid_ln = _ln_fwd(o, x2, gamma.detach(), beta.detach(), eps, p_hidden, 0.0, True)
         ctx.save_for_backward(x16, q16, kv16, ctx16, lse, mask2, z, mean, rstd, wq, bq, wo, bo, gamma)
         ctx.ln_params = (gamma, beta, bo)
@@ -386,8 +395,9 @@ class FfnBlockFn(torch.autograd.Function):
         else:        # inference (rollout, validation): nobody reads gelu' -- one M x 3072 image less to write
             pre = None
             gemm(x16[:M], weight_operand(w1, "bf16"), g16[:M], bias=b1.detach(), epilogue=L.EPI_GELU)
-        o = torch.empty(M, H, dtype=O_DTYPE, device=dev)      # bf16: what a linear returns under autocast (ops._ln_fwd reads it as such)
+        o = torch.empty(M, H, dtype=_o_dtype(w2), device=dev)      # bf16: what a linear returns under autocast (ops._ln_fwd reads it as such)
         gemm(g16[:M], weight_operand(w2, "bf16"), o, bias=b2.detach())
+        if audit.ACTIVE is not None: ops.range_audit(o, audit.ACTIVE.row(w2))
         y, y16, z, mean, rstd, cid_ln = _ln_fwd(o, x2, gamma.detach(), beta.detach(), eps, p_hidden, 0.0, True)
         ctx.save_for_backward(x16, g16, pre, z, mean, rstd, w1, b1, w2, b2, gamma)
         ctx.ln_params = (gamma, beta, b2)

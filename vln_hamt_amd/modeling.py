@@ -47,6 +47,8 @@ class HamtPreTrainedModel(nn.Module):
     def __init__(self, config, *inputs, **kwargs):
         super().__init__()
         self.config = config
+        from . import audit
+        audit.note_model(self)          # (a weak reference: how the HAMT_HALF_WATCH=1 watch names its rows)
 
     # ---- initialisation (HF-4.x BERT recipe)
     def _init_weights(self, module):

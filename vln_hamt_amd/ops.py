@@ -1855,3 +1855,27 @@ def eval_mse_cols(x, t, acc):
         return acc
     L.check(L.load().hamt_eval_mse_cols(R, Cc, _p(x), ldx, _p(t), ldt, _p(acc.sums), _stream()), "hamt_eval_mse_cols")
     return acc
+
+
+# ------------------------------------------------------------------------------------------ range watch on a dense output
+RANGE_REC = 4               # int64 rec[4]: at the limit, non-finite, float32 bits of the largest finite |x|, calls (include/hamt.h: hamt_range_audit)
+
+
+@torch.no_grad()
+def range_audit(t, rec):
+    """Fold the 2-D fp16 / bf16 / fp32 tensor `t` (unit inner stride, any row stride) into the device record `rec` (int64 [4], contiguous):
+    rec[0] += elements with |x| == 65504 (half only: what the clamped store turns an overflow into), rec[1] += non-finite elements,
+    rec[2] = max(rec[2], float32 bits of the largest finite |x|), rec[3] += 1.  One launch on the current stream, nothing read back."""
+    _chk(t, "range_audit")
+    dev = t.device
+    if t.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise L.HamtError(f"range_audit: t must be fp16, bf16 or fp32, got {t.dtype}")
+    ld = _eval_rows("range_audit", t, "t", dev, t.dtype)
+    if not torch.is_tensor(rec) or rec.dtype != torch.int64 or rec.device != dev or tuple(rec.shape) != (RANGE_REC,) or not rec.is_contiguous():
+        raise L.HamtError(f"range_audit: rec must be a contiguous int64 [{RANGE_REC}] tensor on {dev}")
+    M, N = t.shape
+    if N == 0:
+        raise L.HamtError("range_audit: t has no columns")
+    # (a tensor without rows has no data pointer; the call still counts, and reads nothing through the stand-in)
+    L.check(L.load().hamt_range_audit(_p(t) if M > 0 else _p(rec), _dt(t), M, N, ld, _p(rec), _stream()), "hamt_range_audit")
+    return rec
