@@ -120,7 +120,15 @@ int hamt_gemm(const hamt_gemm_desc* d, const void* A, const void* B, void* C, co
               void* aux, void* stream);
 /* Same, with a caller-provided fp32 workspace that enables deterministic split-K for small outputs with a long
  * reduction (weight gradients: dW[768,768] = dY^T X over K = B*L rows).  hamt_gemm_ksplit() tells how many K
- * slices S the kernel would use for `d`; pass ws_bytes >= S*M*N*4 (less => fewer slices; NULL => no split). */
+ * slices S the kernel would use for `d`; pass ws_bytes >= S*M*N*4 (less => fewer slices; NULL => no split).
+ * A problem splits only with the plain or the HAMT_EPI_ACCUM epilogue into a dense fp32 C (ldc == N).  Slice s stores
+ * alpha * (its part of the reduction) as an [M][N] fp32 tile at ws + s*M*N -- alpha is applied there, once per slice --
+ * and a second kernel adds the S tiles in a fixed order (+ C under HAMT_EPI_ACCUM): slice order 0, 1, 2, ... when
+ * M*N % 4 == 0 and ws and C are 16-byte aligned, otherwise four interleaved runs (s = 0, 4, ..; 1, 5, ..; ..) summed as
+ * (r0 + r1) + (r2 + r3).  Deterministic; after the call the first S*M*N floats of ws hold those tiles, and nothing
+ * behind them is written.
+ * (hamt_workspace_bytes(HAMT_WS_GEMM_SPLITK) describes the NT problem {M, N, K} (both operands K-contiguous) only: it
+ * answers 0 for weight-gradient (a_kmajor) shapes that do split.  Size the workspace from hamt_gemm_ksplit, as ops.gemm does.) */
 int hamt_gemm_ksplit(const hamt_gemm_desc* d);
 int hamt_gemm_ws(const hamt_gemm_desc* d, const void* A, const void* B, void* C, const float* bias,
                  void* aux, void* ws, size_t ws_bytes, void* stream);

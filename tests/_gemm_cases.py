@@ -60,11 +60,52 @@ BENCH_GEMMS = [   # (layout, M, N, K, epilogue, C dtype, kernel the launcher mus
     ("nn", 5120, 768, 3072, "acc", "f32", "gemm_q4_kernel<8, true>"),
 ]
 
+# Problems that run as K slices over the grid (gemm_ksplit: plain / accumulate epilogue into a dense fp32 C, fewer than 192 tiles of 128
+# rows, a long reduction; TN never takes the K-group kernel instead) followed by hamt_reduce_partials -- what they COMPUTE is checked by
+# test_gpu_splitk.py, that they split as written here by test_gemm_plan.py.  Rows:
+# (switch or None, layout, M, N, K, epilogue, slices of workspace offered or None = as many as hamt_gemm_ksplit asks for, slices, kernel)
+def _sk(layout, bm, epi):
+    return f"gemm_fast_kernel<{bm}, {EPI_OF[epi]}, {'true' if layout == 'tn' else 'false'}, {'false' if layout == 'nt' else 'true'}>"
+
+
+def _splitk_rows(switch, bm, rows):
+    return [(switch, lay, M, N, K, epi, ws, ks, _sk(lay, bm, epi)) for lay, M, N, K, epi, ws, ks in rows]
+
+
+EPI_OF = {"none": 0, "bias": 1, "acc": 8, "mulaux": 256, "mulaux8": 256, "gelugrad": 129, "gelugrad8": 129, "drop_res": 1 | 512 | 1024}
+SPLITK_GEMMS = _splitk_rows(None, 64, [
+    ("tn", 136, 200, 1024, "none", None, 2),       # the smallest problem that splits by itself
+    ("tn", 136, 200, 1600, "acc", None, 3),        # 25 k-tiles -> 8, 8, 9
+    ("tn", 130, 131, 1600, "none", None, 3),       # N % 4 != 0: element-wise partial store; M N % 4 != 0: the scalar reduce kernel
+    ("tn", 64, 128, 2048, "none", None, 4),        # exactly one tile
+    ("tn", 200, 300, 8192, "none", None, 16),      # the cap
+    ("tn", 200, 300, 8192, "none", 5, 5),          # a smaller workspace than asked for
+    ("tn", 200, 300, 8192, "none", 1, 1),          # room for one slice: no split
+    ("nt", 100, 1100, 1024, "none", None, 2),
+    ("nt", 70, 1030, 1600, "acc", None, 3),        # ragged last column tile, N % 4 != 0
+    ("nn", 70, 1032, 1600, "acc", None, 3),
+    ("nn", 100, 1100, 1024, "none", None, 2),
+    ("nt", 100, 130, 12288, "none", None, 16),     # gemm_kg_variant's "very long reduction" rule (>= 192 k-tiles): not K groups
+    ("nn", 100, 136, 12288, "acc", None, 16),
+    ("nt", 33, 1, 12288, "none", None, 16),        # one output column
+]) + _splitk_rows("HAMT_KS=4", 64, [
+    ("nt", 200, 136, 448, "none", None, 4),        # 7 k-tiles -> 1, 2, 2, 2
+    ("nn", 200, 136, 448, "acc", None, 4),
+    ("tn", 136, 200, 448, "acc", None, 4),
+    ("tn", 200, 136, 128, "none", None, 2),        # one k-tile per slice: nothing behind the ring's prologue
+    ("nt", 300, 200, 320, "none", None, 4),        # 1, 1, 1, 2
+    ("nt", 200, 136, 448, "none", 2, 2),
+]) + _splitk_rows("HAMT_FAST_BM=128", 128, [
+    ("tn", 136, 200, 1600, "none", None, 3), ("nn", 70, 1032, 1600, "acc", None, 3), ("tn", 130, 131, 1600, "none", None, 3),
+]) + _splitk_rows("HAMT_FAST_BM=32", 32, [
+    ("nt", 100, 130, 1024, "none", None, 2), ("nn", 100, 136, 1600, "acc", None, 3), ("nt", 33, 1, 1600, "none", None, 3),
+])
+SPLITK_SWITCHES = ["HAMT_KS=4", "HAMT_FAST_BM=128", "HAMT_FAST_BM=32"]
+
 
 # ---------------------------------------------------------------------------------------------- hamt_gemm_plan, without a GPU
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN_GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_plan_parent.txt")
-EPI_OF = {"none": 0, "bias": 1, "acc": 8, "mulaux": 256, "mulaux8": 256, "gelugrad": 129, "gelugrad8": 129, "drop_res": 1 | 512 | 1024}
 
 
 def plan_desc(GemmDesc, layout, M, N, K, epilogue, dtype_c):
@@ -100,6 +141,24 @@ def plan_mismatches(plan, GemmDesc, rows):
     return bad
 
 
+def splitk_ws_bytes(row, asked):
+    """bytes of workspace a SPLITK_GEMMS row offers; `asked` = the slices hamt_gemm_ksplit answers for its descriptor"""
+    _, _, M, N, _, _, ws_ks, _, _ = row
+    return (asked if ws_ks is None else ws_ks) * M * N * 4
+
+
+def splitk_mismatches(plan, ksplit, GemmDesc, rows, f32=0):
+    """SPLITK_GEMMS rows that `plan(desc, ws_bytes) -> (slices, kernel)` answers differently (`ksplit(desc)`: the slices it asks for)"""
+    bad = []
+    for r in rows:
+        _, layout, M, N, K, epi, _, ks, name = r
+        d = plan_desc(GemmDesc, layout, M, N, K, EPI_OF[epi], f32)
+        got = plan(d, splitk_ws_bytes(r, ksplit(d)))
+        if got != (ks, name):
+            bad.append((r, got))
+    return bad
+
+
 if __name__ == "__main__":      # child of test_gemm_plan.py: the rows of ONE environment setting (already in os.environ), no torch in the process
     sys.path.insert(0, ROOT)
     from vln_hamt_amd import _lib as L
@@ -111,8 +170,13 @@ if __name__ == "__main__":      # child of test_gemm_plan.py: the rows of ONE en
         ks = lib.hamt_gemm_plan(C.byref(d), ws_bytes, buf, 160)
         return ks, buf.value.decode()
 
-    mine = [r for r in plan_golden_rows() if r[0] == sys.argv[1]]
-    bad = plan_mismatches(_plan, L.GemmDesc, mine)
+    if sys.argv[2:] == ["splitk"]:      # the SPLITK_GEMMS rows of this switch instead of the golden record's
+        lib.hamt_gemm_ksplit.argtypes = L.SIGNATURES["hamt_gemm_ksplit"]
+        mine = [r for r in SPLITK_GEMMS if r[0] == sys.argv[1]]
+        bad = splitk_mismatches(_plan, lambda d: lib.hamt_gemm_ksplit(C.byref(d)), L.GemmDesc, mine, L.HAMT_F32)
+    else:
+        mine = [r for r in plan_golden_rows() if r[0] == sys.argv[1]]
+        bad = plan_mismatches(_plan, L.GemmDesc, mine)
     for b in bad[:20]:
         print(b)
     print(f"{sys.argv[1]}: {len(mine)} rows, {len(bad)} mismatches")

@@ -9,7 +9,8 @@ import sys
 
 import pytest
 
-from _gemm_cases import BENCH_GEMMS, EPI_OF, KG_GEMMS, ROOT, plan_desc, plan_golden_rows, plan_mismatches
+from _gemm_cases import (BENCH_GEMMS, EPI_OF, KG_GEMMS, ROOT, SPLITK_GEMMS, SPLITK_SWITCHES, plan_desc, plan_golden_rows, plan_mismatches,
+                         splitk_mismatches)
 
 ENVIRONMENTS = ["default", "HAMT_P8=0", "HAMT_P8=1", "HAMT_Q4=0", "HAMT_Q4=1", "HAMT_KG=1", "HAMT_KG=3223", "HAMT_KG=3232", "HAMT_KG=3224",
                 "HAMT_KG=6423", "HAMT_KG=6432", "HAMT_KG=12822", "HAMT_KG=322", "HAMT_FAST_BM=32", "HAMT_FAST_BM=64", "HAMT_FAST_BM=128",
@@ -80,3 +81,18 @@ def test_golden_under_switch(setting):
     k, v = setting.split("=")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_gemm_cases.py"), setting], env={**os.environ, k: v}, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def test_splitk_cases_split_as_recorded():
+    """SPLITK_GEMMS (the problems test_gpu_splitk.py launches): slices and kernel, with the workspace each row offers.  The rows of the
+    default environment in this process, the rows under a switch in one child per switch."""
+    L = _lib()
+    assert {r[0] for r in SPLITK_GEMMS} == {None, *SPLITK_SWITCHES}
+    rows = [r for r in SPLITK_GEMMS if r[0] is None]
+    bad = splitk_mismatches(lambda d, ws_bytes: L.gemm_plan(d, ws_bytes), lambda d: L.load().hamt_gemm_ksplit(d), L.GemmDesc, rows, L.HAMT_F32)
+    assert not bad, bad
+    assert all(r[8].startswith("gemm_fast_kernel<64, ") for r in rows)      # no 128-row tile splits by itself
+    for setting in SPLITK_SWITCHES:
+        k, v = setting.split("=")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_gemm_cases.py"), setting, "splitk"], env={**os.environ, k: v}, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

@@ -11,7 +11,7 @@ struct GemmArgsF {
   void* C;
   const float* bias;
   void* aux;
-  int ksplit;      // number of K slices (grid.y); > 1 => raw fp32 partials to `part`
+  int ksplit;      // number of K slices (grid.y); > 1 => fp32 partial tiles (alpha x the slice's sum) to `part`
   float* part;
   int ka_max, kb_max;   // last valid reduction row of a K-strided A / B (rows beyond are clamped to it)
   float p_drop;         // HAMT_EPI_DROPOUT

@@ -211,9 +211,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgsF& g, int m0, int n0, in
       for (int j = 0; j < FN; ++j) {
         const int row = m0 + wm * TM + i * 16 + (lane & 15), col = n0 + wn * TN + j * 16 + (lane >> 4) * 4;
         const float a4[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        if (g.ksplit > 1) {
+        if (g.ksplit > 1) {   // (see the staged branch below: alpha x the slice's sum)
           float* P = g.part + (size_t)slice * g.M * g.N;
-          if (row < g.M) for (int e = 0; e < 4; ++e) if (col + e < g.N) P[(size_t)row * g.N + col + e] = a4[e];
+          if (row < g.M) for (int e = 0; e < 4; ++e) if (col + e < g.N) P[(size_t)row * g.N + col + e] = g.alpha * a4[e];
         } else epi_store<EPI, 4>(g, row, col, a4, (COLSUM && g.ss) ? &tile_ssq : nullptr);
       }
     if constexpr (COLSUM) { if (g.ss) tile_sumsq_store(g, m0, n0, tile_ssq, (float*)lds); }
@@ -272,11 +272,14 @@ __device__ __forceinline__ void gemm_tile(const GemmArgsF& g, int m0, int n0, in
       const f32x4 lo = *(const f32x4*)(ct + rl * BN + (((2 * c8) ^ (rl & 7)) << 2));
       const f32x4 hi = *(const f32x4*)(ct + rl * BN + (((2 * c8 + 1) ^ (rl & 7)) << 2));
       const float v8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      if (g.ksplit > 1) {   // raw partial tile, combined (and epilogued) by the reduce pass
-        float* P = g.part + (size_t)slice * g.M * g.N;
+      if (g.ksplit > 1) {   // partial tile = alpha x this slice's sum (the only epilogue step a split problem has besides the accumulate:
+        float* P = g.part + (size_t)slice * g.M * g.N;      // gemm_ksplit), so that the reduce pass stays a pure ordered sum (+ C)
+        float s8[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s8[e] = g.alpha * v8[e];
         if (row < g.M) {
-          if (col + 8 <= g.N && (g.N & 3) == 0) st_f<8>(P + (size_t)row * g.N + col, v8);
-          else for (int e = 0; e < 8; ++e) if (col + e < g.N) P[(size_t)row * g.N + col + e] = v8[e];
+          if (col + 8 <= g.N && (g.N & 3) == 0) st_f<8>(P + (size_t)row * g.N + col, s8);
+          else for (int e = 0; e < 8; ++e) if (col + e < g.N) P[(size_t)row * g.N + col + e] = s8[e];
         }
       } else if constexpr (PRE_AUX) epi_store<EPI, 8>(g, row, col, v8, (COLSUM && g.ss) ? &tile_ssq : nullptr, &pa[p], nullptr, pre_ok);
       else epi_store<EPI, 8>(g, row, col, v8, (COLSUM && g.ss) ? &tile_ssq : nullptr);
