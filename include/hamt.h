@@ -782,6 +782,47 @@ int hamt_obj_gather(int B, int Ow, int Fo, int A, int S, int64_t NV, int64_t NOb
                     const int32_t* scan_n, const int32_t* ep_scan, const int32_t* cur, const int32_t* view, float* obj_feats,
                     float* obj_angles, float* obj_poses, uint8_t* obj_masks, int32_t* obj_lens, int32_t* obj_ids, int32_t* anomalies,
                     void* stream);
+/* The batch a PRETRAINING step consumes, gathered from resident tables in one launch (csrc/pretrain_gather.hip; what
+ * pretrain_src/data/r2r_data.py::MultiStepNavData.get_input, the task datasets' corruption and the *_collate padding of r2r_tasks.py build
+ * on the host).  Viewpoint tables, NV rows: feat fp32 [NV, 36, F]; prob fp32 [NV, 36, P] (soft labels, may be NULL); ang36 fp32
+ * [36, 36, A]; cand_cnt int32 [NV]; cand_view int32 [NV, C] (each candidate's view); cand_ang fp32 [NV, C, 12, A] (its angle feature per
+ * base heading).  Step tables, NS rows, the trajectories back to back: step_idx int32 [NS, 4] = (viewpoint row, view looked at, action
+ * label in the 36-view layout, action label in the candidates-first layout); step_val fp32 [NS, A + 5] = (the A-wide action angle
+ * feature the step leaves in the history, action angles [2] in the 36-view layout, action angles [2] in the candidates-first layout,
+ * progress).  sp_table fp32 [36, 36, 2] (may be NULL without sp_targets).  records int32 [B, HAMT_PRETRAIN_RECORD]: (first step row of
+ * the trajectory, history length t, flag bits HAMT_PRETRAIN_KILL_*, MRC mask: bit s zeroes history step s, SPREL anchor, then words the
+ * kernel does not read).
+ *
+ * History step s < t of sample b is step row base + s: hist_img [B, Hmax, F] = feat[row, view], hist_ang [B, Hmax, A] = the step's angle
+ * feature, hist_pano_img [B, Hmax, 36, F] = feat[row], hist_pano_ang [B, Hmax, 36, A] = ang36[view], hist_prob [B, Hmax, P] =
+ * prob[row, view], hist_mrc uint8 [B, Hmax] = the mask bit; a masked step's hist_img and hist_pano_img rows are zeros.  hist_masks uint8
+ * [B, Hmax + 1] = 1 for the first t + 1 slots (the cls slot), hist_lens int64 [B] = t + 1.  The observation is step row base + t, W = Omax
+ * slots: HAMT_PRETRAIN_VIEWS36 = the 36 views in their own order (nav type 1 where a candidate points) and STOP (zeros, nav type 2);
+ * HAMT_PRETRAIN_CANDS_FIRST = hamt_obs_gather's HAMT_OBS_PANO order.  ob_img [B, W, F], ob_ang [B, W, A], ob_nav int64 [B, W], ob_masks
+ * uint8 [B, W], ob_lens int64 [B]; HAMT_PRETRAIN_KILL_V zeroes the sample's ob_img, HAMT_PRETRAIN_KILL_A its ob_ang.  act_view int64 [B],
+ * act_ang fp32 [B, 2], progress fp32 [B]: the observed step's labels for `layout`; anchor int64 [B] and sp_targets fp32 [B, 36, 2] =
+ * sp_table[anchor].  NULL outputs are skipped: the hist_* rows with Hmax = 0, the panorama pair, hist_prob / hist_mrc, the five
+ * observation outputs (together; the labels need them), each label; hist_masks and hist_lens are always written.  Every element of every
+ * output given is written by every call.  Nothing a record points to is trusted: a base or history length outside [0, NS] / [0, Hmax], an
+ * anchor outside [0, 36) (with sp_targets), or a reached step row whose viewpoint row is outside [0, NV) or whose view is outside [0, 36)
+ * is found BEFORE any table load; that sample is zeros everywhere (hist_masks 1 in the cls slot only, hist_lens 1, ob_masks and ob_lens 0,
+ * labels 0) and anomalies[0] += 1.  Hmax above HAMT_PRETRAIN_MAX_HIST, C above HAMT_PRETRAIN_MAX_CAND or Omax above 37 + HAMT_PRETRAIN_MAX_CAND:
+ * HAMT_ERR_UNSUPPORTED, nothing launched.  Rows are copied 16 bytes per lane where F (P) % 4 == 0 and the bases are 16-byte aligned, element by element otherwise;
+ * offsets into feat and prob are 64-bit; no arithmetic touches a value. */
+#define HAMT_PRETRAIN_VIEWS36 0
+#define HAMT_PRETRAIN_CANDS_FIRST 1
+#define HAMT_PRETRAIN_KILL_V 1
+#define HAMT_PRETRAIN_KILL_A 2
+#define HAMT_PRETRAIN_RECORD 8
+#define HAMT_PRETRAIN_MAX_HIST 32
+#define HAMT_PRETRAIN_MAX_CAND 64
+int hamt_pretrain_gather(int B, int Hmax, int Omax, int F, int A, int P, int C, int layout, int64_t NV, int64_t NS, const float* feat,
+                         const float* prob, const float* ang36, const int32_t* cand_cnt, const int32_t* cand_view, const float* cand_ang,
+                         const int32_t* step_idx, const float* step_val, const float* sp_table, const int32_t* records, float* hist_img,
+                         float* hist_ang, float* hist_pano_img, float* hist_pano_ang, float* hist_prob, uint8_t* hist_mrc,
+                         uint8_t* hist_masks, int64_t* hist_lens, float* ob_img, float* ob_ang, int64_t* ob_nav, uint8_t* ob_masks,
+                         int64_t* ob_lens, int64_t* act_view, float* act_ang, float* progress, int64_t* anchor, float* sp_targets,
+                         int32_t* anomalies, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * optimiser side (A24): global L2 norm over a flat gradient arena, then the reference's HF AdamW

@@ -186,6 +186,7 @@ SIGNATURES = {
     "hamt_obs_gather": [i32, i32, i32, i32, i32, i32] + [vp] * 24,
     "hamt_obs_turn": [i32, i32] + [vp] * 5,
     "hamt_obj_gather": [i32, i32, i32, i32, i32, C.c_int64, C.c_int64] + [vp] * 19,
+    "hamt_pretrain_gather": [i32] * 8 + [C.c_int64] * 2 + [vp] * 30,
     "hamt_sumsq": [sz, vp, vp, i32, vp, vp],
     "hamt_sumsq_table": [sz, sz, vp, vp, vp, i32, vp, i32, vp, vp],
     "hamt_sumsq_partials": [sz, vp, vp, i32, vp],

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libhamt_hip.so")
-SOURCES = ["abi.hip", "gemm.hip", "gemm_fast.hip", "gemm_q4.hip", "attn.hip", "attn16.hip", "attn_cls.hip", "norm.hip", "vis_embed.hip", "obj_embed.hip", "elementwise.hip", "image_prep.hip", "image_resample.hip", "loss.hip", "eval.hip", "policy.hip", "nav.hip", "obs.hip", "optim.hip", "audit.hip"]
+SOURCES = ["abi.hip", "gemm.hip", "gemm_fast.hip", "gemm_q4.hip", "attn.hip", "attn16.hip", "attn_cls.hip", "norm.hip", "vis_embed.hip", "obj_embed.hip", "elementwise.hip", "image_prep.hip", "image_resample.hip", "loss.hip", "eval.hip", "policy.hip", "nav.hip", "obs.hip", "pretrain_gather.hip", "optim.hip", "audit.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"] + os.environ.get("HAMT_EXTRA_FLAGS", "").split()
 
 

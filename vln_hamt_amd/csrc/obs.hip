@@ -12,7 +12,7 @@
 // candidate views by an OR over lanes, the rank of a free view by a population count) and copies the row with 16 bytes per lane when
 // F % 4 == 0 and the bases are aligned, element by element otherwise (and for the A-wide angle rows).  Wave shuffles only: no LDS, no
 // hand-off between waves; the only atomic is the anomaly counter.  Offsets into feat are 64-bit.
-#include "common.h"
+#include "row_copy.h"          // wave_or_u, copy_row, aligned16
 
 namespace {
 
@@ -20,24 +20,6 @@ constexpr int kWaves = 4;                          // rows per 256-thread workgr
 constexpr int kViews = 36;
 constexpr int kHeadings = 12;
 constexpr int kMaxRowBlocks = 64;                  // row blocks per episode; more rows than 64 * kWaves are strided over
-
-__device__ __forceinline__ uint32_t wave_or_u(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
-// dst[0..n) = src[0..n), or zeros for a NULL src
-__device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* __restrict__ src, int n, bool vec, int lane) {
-  if (vec) {
-    f32x4* __restrict__ d = reinterpret_cast<f32x4*>(dst);
-    const f32x4* __restrict__ s = reinterpret_cast<const f32x4*>(src);
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int i = lane; i < (n >> 2); i += 64) d[i] = src ? s[i] : zero;
-  } else {
-    for (int i = lane; i < n; i += 64) dst[i] = src ? src[i] : 0.0f;
-  }
-}
 
 __global__ __launch_bounds__(64 * kWaves) void obs_gather_kernel(
     int B, int W, int F, int A, int C, int layout, int vec, const float* __restrict__ feat, const float* __restrict__ ang36,
@@ -167,8 +149,6 @@ __global__ __launch_bounds__(64 * kWaves) void obj_gather_kernel(
     }
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

@@ -44,6 +44,15 @@ def _standardize_radians(x):
     return np.where(x >= np.pi, x - 2 * np.pi, x)
 
 
+def sprel_target_table():
+    """float64 [36, 36, 2]: sp_targets[anchor, view] = (heading, elevation) of `view` relative to `anchor`, wrapped into [-pi, pi)
+    (r2r_tasks.py:498-512)"""
+    step = math.radians(30)
+    head = np.array([(v % 12) * step for v in range(36)])
+    elev = np.array([(v // 12 - 1) * step for v in range(36)])
+    return _standardize_radians(np.stack([head[None, :] - head[:, None], elev[None, :] - elev[:, None]], -1))
+
+
 class _NavTaskDataset(Dataset):
     """`per_step`: one item per (trajectory, instruction, step) -- the observation tasks -- instead of one per (trajectory,
     instruction) with the whole path as history."""
@@ -184,11 +193,7 @@ class SprelDataset(SapDataset):
 
     def __init__(self, nav_db, tok, random_kill_v, random_kill_a):
         super().__init__(nav_db, tok, random_kill_v, random_kill_a)
-        step = math.radians(30)
-        head = np.array([(v % 12) * step for v in range(36)])
-        elev = np.array([(v // 12 - 1) * step for v in range(36)])
-        # sp_targets[anchor, view] = (heading, elevation) of `view` relative to `anchor`, wrapped into [-pi, pi)
-        self.sp_targets = _standardize_radians(np.stack([head[None, :] - head[:, None], elev[None, :] - elev[:, None]], -1))
+        self.sp_targets = sprel_target_table()
 
     def _labels(self, inputs, out):
         pass

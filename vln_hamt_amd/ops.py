@@ -1751,6 +1751,53 @@ def obj_gather(store, ep_scan, cur, view, out, anomalies):
     return out
 
 
+PRETRAIN_LAYOUTS = {"views36": 0, "cands_first": 1}            # HAMT_PRETRAIN_VIEWS36 / _CANDS_FIRST
+PRETRAIN_RECORD, PRETRAIN_MAX_HIST = 8, 32                     # HAMT_PRETRAIN_RECORD / _MAX_HIST
+PRETRAIN_OUTPUTS = ("hist_img_fts", "hist_ang_fts", "hist_pano_img_fts", "hist_pano_ang_fts", "hist_img_probs", "hist_mrc_masks", "hist_masks",
+                    "hist_lens", "ob_img_fts", "ob_ang_fts", "ob_nav_types", "ob_masks", "ob_lens", "ob_action_viewindex", "ob_action_angles",
+                    "ob_progress", "sp_anchor_idxs", "sp_targets")                   # hamt_pretrain_gather's outputs, in its order
+
+
+def pretrain_gather(store, records, out, Hmax, Omax, layout=0):
+    """One pretraining batch, one launch (csrc/pretrain_gather.hip): for the B samples of `records` int32 [B, 8] (data/device_tasks.py),
+    what MultiStepNavData.get_input, the task datasets and their collate functions build on the host, gathered from `store` (a
+    data.device_store.PretrainStore).  `out`: {name: tensor} over PRETRAIN_OUTPUTS, a missing or None entry = an output the task does not
+    have; shapes as the collated batch has them (hist_* [B, Hmax, ...], hist_masks [B, Hmax + 1], ob_* [B, Omax, ...], masks bool, lengths
+    and indices int64), every element of which is overwritten.  A record pointing outside the tables gives a sample of zeros and adds 1
+    to `store.anomalies`.  Nothing is read from the host."""
+    _chk(records, "pretrain_gather")
+    dev, B, F, A, P = records.device, records.shape[0], store.F, store.A, store.P
+    _nav_arg("pretrain_gather: records", records, torch.int32, (B, PRETRAIN_RECORD), dev)
+    if store.device != dev:
+        raise L.HamtError(f"pretrain_gather: the store is on {store.device}, the records on {dev}")
+    Hmax, Omax, layout = int(Hmax), int(Omax), PRETRAIN_LAYOUTS.get(layout, layout)
+    if not 0 <= Hmax <= PRETRAIN_MAX_HIST or Omax < 0 or layout not in (0, 1):
+        raise L.HamtError(f"pretrain_gather: Hmax {Hmax} outside [0, {PRETRAIN_MAX_HIST}], Omax {Omax} < 0 or layout {layout} unknown")
+    shapes = {"hist_img_fts": (torch.float32, (B, Hmax, F)), "hist_ang_fts": (torch.float32, (B, Hmax, A)),
+              "hist_pano_img_fts": (torch.float32, (B, Hmax, OBS_VIEWS, F)), "hist_pano_ang_fts": (torch.float32, (B, Hmax, OBS_VIEWS, A)),
+              "hist_img_probs": (torch.float32, (B, Hmax, P)), "hist_mrc_masks": (torch.bool, (B, Hmax)), "hist_masks": (torch.bool, (B, Hmax + 1)),
+              "hist_lens": (torch.int64, (B,)), "ob_img_fts": (torch.float32, (B, Omax, F)), "ob_ang_fts": (torch.float32, (B, Omax, A)),
+              "ob_nav_types": (torch.int64, (B, Omax)), "ob_masks": (torch.bool, (B, Omax)), "ob_lens": (torch.int64, (B,)),
+              "ob_action_viewindex": (torch.int64, (B,)), "ob_action_angles": (torch.float32, (B, 2)), "ob_progress": (torch.float32, (B,)),
+              "sp_anchor_idxs": (torch.int64, (B,)), "sp_targets": (torch.float32, (B, OBS_VIEWS, 2))}
+    unknown = set(out) - set(shapes)
+    if unknown:
+        raise L.HamtError(f"pretrain_gather: unknown outputs {sorted(unknown)}")
+    ptrs = []
+    for name in PRETRAIN_OUTPUTS:
+        t_ = out.get(name)
+        if t_ is not None:
+            _nav_arg("pretrain_gather: " + name, t_, shapes[name][0], shapes[name][1], dev)
+        ptrs.append(_p(t_))
+    if out.get("hist_img_probs") is not None and store.prob is None:
+        raise L.HamtError("pretrain_gather: hist_img_probs asked of a store built without the soft labels (with_probs=False)")
+    L.check(L.load().hamt_pretrain_gather(B, Hmax, Omax, F, A, P, store.C, layout, store.NV, store.NS, _p(store.feat), _p(store.prob),
+                                          _p(store.ang36), _p(store.cand_cnt), _p(store.cand_view), _p(store.cand_ang), _p(store.step_idx),
+                                          _p(store.step_val), _p(store.sp_targets), _p(records), *ptrs, _p(store.anomalies), _stream()),
+            "hamt_pretrain_gather")
+    return out
+
+
 def kl_div_logsoftmax(x, t):
     return KlFn.apply(x, t)
 
