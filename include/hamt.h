@@ -57,7 +57,9 @@ int hamt_version(void);
 /* copies the calling thread's last error text into buf (NUL terminated); returns its length */
 int hamt_last_error(char* buf, size_t n);
 /* name (as rocprofv3 prints it, template arguments included) of the kernel the calling thread's most recent hamt_gemm /
- * hamt_gemm_ws call launched for its contraction -- lets a profiler attribute recorded calls to kernel-trace rows */
+ * hamt_gemm_ws call launched for its contraction -- lets a profiler attribute recorded calls to kernel-trace rows.  A bf16-path
+ * attention backward (hamt_attn_small_bwd, hamt_attn_varlen_bwd, hamt_attn_varlen_cross_bwd) leaves its kernel here too, by family:
+ * attn_s128_bwd_kernel, attn_wide_bwd_kernel, attn_wide_bwd_kernel<packed> (a packed call with a side above 128), attn16_bwd_kernel. */
 int hamt_last_kernel(char* buf, size_t n);
 /* Caller-provided scratch sizes (the library never allocates).  shape[] by op:
  *   HAMT_WS_GEMM_SPLITK  {M, N, K}  bytes hamt_gemm_ws can use for its deterministic split-K (0: it will not split)
@@ -238,7 +240,7 @@ int hamt_attn_small_bwd(const hamt_attn_desc* d, const void* q, const void* k, c
 int hamt_attn_cls_fwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v, void* o, void* stream);
 
 /* Packed ("varlen") self-attention, bf16 path: the B sequences lie back to back, sample b owns rows [cu_seqlens[b], cu_seqlens[b + 1])
- * of q / k / v / o / d_o / dq / dk / dv (row strides as in the descriptor), at most d->Sq = d->Sk <= 128 tokens each, every key real (no
+ * of q / k / v / o / d_o / dq / dk / dv (row strides as in the descriptor), at most d->Sq = d->Sk <= 256 tokens each, every key real (no
  * mask); lse is [B, heads, d->Sq].  = hamt_attn_small_* on the real tokens of a padded batch (vilmodel.py:96-129) without computing
  * the padded rows; a sequence of length 0 is skipped. */
 int hamt_attn_varlen_fwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v, const int* cu_seqlens,
@@ -257,7 +259,7 @@ int hamt_attn_varlen_bwd(const hamt_attn_desc* d, const void* q, const void* k, 
  * (cu_q form: rows [pair[b] * Sk, ...) and row pair[b] of add_mask) or the entry of cu_k (cu_k form); negative = a filler.  Every key
  * side must be named by at most one query sequence (dk / dv are stored, not accumulated).  For packed copies of a batch whose fillers lie
  * between the copies (forward_itm's replicated text, vilmodel.py:672-676).
- * lse is [B, heads, d->Sq] in both forms. */
+ * lse is [B, heads, d->Sq] in both forms.  d->Sq, d->Sk <= 256 (more: HAMT_ERR_ARG, nothing is launched). */
 int hamt_attn_varlen_cross_fwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v, const int* cu_q,
                                const int* cu_k, int n_pairs, const int* pair, const float* add_mask, void* o, float* lse,
                                const uint64_t* rng, void* stream);

@@ -239,7 +239,8 @@ def last_error() -> str:
 
 
 def last_kernel() -> str:
-    """kernel the most recent hamt_gemm call of this thread launched (rocprofv3's name, template arguments included)"""
+    """kernel the most recent hamt_gemm call of this thread launched (rocprofv3's name, template arguments included), or the kernel family
+    of its most recent bf16-path attention backward"""
     buf = C.create_string_buffer(160)
     load().hamt_last_kernel(buf, 160)
     return buf.value.decode(errors="replace")

@@ -338,13 +338,13 @@ void hamt_attn16_bwd_launch(const hamt_attn_desc* d, const void* q, const void* 
                             const int* cu_q = nullptr, const int* cu_k = nullptr, int n_pairs = 0, const int* pair = nullptr);
 
 // Packed ("varlen") self-attention: the B sequences lie back to back, sample b owns rows [cu[b], cu[b + 1]) of q / k / v / o (every
-// one of its keys is real: no mask), at most d->Sq = d->Sk <= 128 rows each; lse is [B, heads, d->Sq].  What BertSelfAttention
+// one of its keys is real: no mask), at most d->Sq = d->Sk <= 256 rows each; lse is [B, heads, d->Sq].  What BertSelfAttention
 // (vilmodel.py:96-129) computes for the REAL tokens of a padded batch, without the padded rows.
 static int check_varlen(const hamt_attn_desc* d, const int* cu, const char* who) {
   int rc = check_desc(d, who);
   if (rc) return rc;
   HAMT_CHECK_ARG(cu != nullptr, "%s: cu_seqlens is null", who);
-  HAMT_CHECK_ARG(d->prec == HAMT_PREC_BF16 && d->Sq == d->Sk && d->Sq <= 128, "%s: packed attention is built for the bf16 path, self-attention, <= 128 tokens per sequence (Sq %d, Sk %d)", who, d->Sq, d->Sk);
+  HAMT_CHECK_ARG(d->prec == HAMT_PREC_BF16 && d->Sq == d->Sk && d->Sq <= 256, "%s: packed attention is built for the bf16 path, self-attention, <= 256 tokens per sequence (Sq %d, Sk %d)", who, d->Sq, d->Sk);
   return HAMT_OK;
 }
 extern "C" int hamt_attn_varlen_fwd(const hamt_attn_desc* d, const void* q, const void* k, const void* v, const int* cu_seqlens,
@@ -379,7 +379,7 @@ static int check_varlen_cross(const hamt_attn_desc* d, const int* cu_q, const in
   int rc = check_desc(d, who);
   if (rc) return rc;
   HAMT_CHECK_ARG((cu_q != nullptr) != (cu_k != nullptr), "%s: exactly one of cu_q / cu_k must be given", who);
-  HAMT_CHECK_ARG(d->prec == HAMT_PREC_BF16 && d->Sq <= 128 && d->Sk <= 128, "%s: packed attention is built for the bf16 path, <= 128 tokens per sequence (Sq %d, Sk %d)", who, d->Sq, d->Sk);
+  HAMT_CHECK_ARG(d->prec == HAMT_PREC_BF16 && d->Sq <= 256 && d->Sk <= 256, "%s: packed attention is built for the bf16 path, <= 256 tokens per sequence (Sq %d, Sk %d)", who, d->Sq, d->Sk);
   HAMT_CHECK_ARG(pair != nullptr || (n_pairs >= 0 && n_pairs <= d->B && (cu_k == nullptr || n_pairs == d->B)), "%s: n_pairs = %d outside [0, B = %d] (packed keys: every query sample has keys)", who, n_pairs, d->B);
   return HAMT_OK;
 }

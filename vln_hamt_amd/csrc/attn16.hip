@@ -699,14 +699,35 @@ __global__ __launch_bounds__(512) void attn_s128_bwd_kernel(Attn16Args a) {
 // No barrier between the phases, no LDS traffic but fragment reads.  Same dropout stream as every other attention kernel: phase B
 // redoes the hash of (query row, group of 4 keys) and picks its key's 16 bits.  (For <= 128 tokens this form was measured against
 // the kernel above and lost: profiles/r03_attn_bwd_recompute.txt.)
-template <typename TI, typename TO>
+// PACKED: the packed forms (hamt_attn_varlen_*) with up to 256 rows on a side -- one workgroup per (head, query sequence) on the sequence's
+// own rows (148 KB of LDS at 256 x 256, sixteen waves); lse and the dropout row are indexed by the sequence and the DESCRIPTOR's Sq as in
+// the forward.  dk / dv are stored by the one workgroup whose query sequence names the key side; an empty sequence is skipped, a filler
+// writes zero dq (as in attn_s128_bwd_kernel, the path of the packed calls with both sides <= 128).
+template <typename TI, typename TO, bool PACKED>
 __global__ __launch_bounds__(1024) void attn_wide_bwd_kernel(Attn16Args a) {
   extern __shared__ __attribute__((aligned(16))) bf16_t sm[];
   const hamt_attn_desc& d = a.d;
   const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, w = t >> 6, l15 = lane & 15, g = lane >> 4;
   const int h = blockIdx.x, b = blockIdx.y;
-  const int Sq = d.Sq, Sk = d.Sk;
-  const size_t qrow0 = (size_t)b * d.Sq, krow0 = (size_t)b * d.Sk;
+  int Sq = d.Sq, Sk = d.Sk;
+  size_t qrow0 = (size_t)b * d.Sq, krow0 = (size_t)b * d.Sk;
+  const float* mask = a.mask;
+  int mrow = b;                                        // the key side: the row of the mask
+  if constexpr (PACKED) {
+    if (a.cu_q) { const int c0 = a.cu_q[b]; Sq = a.cu_q[b + 1] - c0; qrow0 = (size_t)c0; }
+    if (Sq <= 0) return;
+    mrow = a.pair ? a.pair[b] : b;
+    const bool filler = a.pair ? mrow < 0 : b >= a.n_pairs;
+    if (!filler) {
+      krow0 = (size_t)mrow * d.Sk;
+      if (a.cu_k) { const int c0 = a.cu_k[mrow]; Sk = a.cu_k[mrow + 1] - c0; krow0 = (size_t)c0; mask = nullptr; }
+    }
+    if (filler || Sk <= 0) {   // a filler query sequence: zero query gradients, no keys to give gradients to
+      TI* dQ0 = (TI*)a.dq + qrow0 * d.ldq + h * 64;
+      for (int i = t; i < Sq * 16; i += nt) st4<TI>(dQ0 + (size_t)(i >> 4) * d.ldq + (i & 15) * 4, 0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+  }
   const int nqb = (Sq + 15) >> 4, nkb = (Sk + 15) >> 4, sq16 = nqb * 16, sk16 = nkb * 16;
   bf16_t* Qs = sm;
   bf16_t* dOs = Qs + sq16 * AST;
@@ -730,7 +751,7 @@ __global__ __launch_bounds__(1024) void attn_wide_bwd_kernel(Attn16Args a) {
     rows_load<TO, 2>(O, d.ldo, Sq, t, nt, ro);
     rows_load<TI, 2>(K, d.ldk, Sk, t, nt, rk);
     rows_load<TI, 2>(V, d.ldv, Sk, t, nt, rv);
-    stage_mask(a.mask, b, Sk, sk16, mk_s, t, nt);
+    stage_mask(mask, mrow, Sk, sk16, mk_s, t, nt);
     for (int i = t; i < sq16; i += nt) rowh_s[i] = hamt_mix32((uint32_t)((b * d.heads + h) * d.Sq + i) ^ key.k0);
     rows_store<TI, 2>(rq, sq16, Qs, t, nt);
     rows_store<TO, 2>(rdo, sq16, dOs, t, nt);
@@ -863,18 +884,21 @@ __global__ __launch_bounds__(1024) void attn_wide_bwd_kernel(Attn16Args a) {
   }
 }
 
-template <typename TI, typename TO>
-void launch_wide_bwd(const Attn16Args& a, hipStream_t s) {
+size_t wide_bwd_lds(const hamt_attn_desc& d) {       // Q, dO, K, V as bf16 rows of AST and lse, delta, the dropout row hash, the mask
+  const int sq16 = (d.Sq + 15) / 16 * 16, sk16 = (d.Sk + 15) / 16 * 16;
+  return (size_t)2 * (sq16 + sk16) * AST * sizeof(bf16_t) + (size_t)(3 * sq16 + sk16) * sizeof(float);
+}
+
+template <typename TI, typename TO, bool PACKED>
+void launch_wide_bwd(const Attn16Args& a, hipStream_t s) {   // (PACKED: the descriptor holds the longest sequence of either side, <= 256)
   const hamt_attn_desc& d = a.d;
   const int nqb = (d.Sq + 15) / 16, nkb = (d.Sk + 15) / 16, nb = nqb > nkb ? nqb : nkb;
-  const int sq16 = nqb * 16, sk16 = nkb * 16;
-  const size_t lds = (size_t)2 * (sq16 + sk16) * AST * sizeof(bf16_t) + (size_t)(3 * sq16 + sk16) * sizeof(float);
   static bool raised = false;                      // > 64 KiB of dynamic LDS needs the opt-in once per kernel
   if (!raised) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_wide_bwd_kernel<TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_wide_bwd_kernel<TI, TO, PACKED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     raised = true;
   }
-  hipLaunchKernelGGL((attn_wide_bwd_kernel<TI, TO>), dim3(d.heads, d.B), dim3(64 * nb), lds, s, a);
+  hipLaunchKernelGGL((attn_wide_bwd_kernel<TI, TO, PACKED>), dim3(d.heads, d.B), dim3(64 * nb), wide_bwd_lds(d), s, a);
 }
 
 template <typename TI, typename TO, int KB, int IT>
@@ -978,7 +1002,16 @@ void hamt_attn16_bwd_launch(const hamt_attn_desc* d, const void* q, const void* 
   const int* cu = cu_q ? cu_q : cu_k;
   dim3 grid(d->heads, d->B), block(256);
   const bool ib = d->dtype_qkv == HAMT_BF16, ob = d->dtype_o == HAMT_BF16;
+  if (cu && (d->Sq > 128 || d->Sk > 128)) {   // a packed call with a long side (the entry points admit <= 256)
+    hamt_set_last_kernel("attn_wide_bwd_kernel<packed>");
+    if (!ib && !ob) launch_wide_bwd<float, float, true>(a, s);
+    else if (ib && ob) launch_wide_bwd<bf16_t, bf16_t, true>(a, s);
+    else if (ib) launch_wide_bwd<bf16_t, float, true>(a, s);
+    else launch_wide_bwd<float, bf16_t, true>(a, s);
+    return;
+  }
   if (use_s128_bwd(d) || cu) {
+    hamt_set_last_kernel("attn_s128_bwd_kernel");
     if (!ib && !ob) launch_s128_bwd<float, float>(a, s);
     else if (ib && ob) launch_s128_bwd<bf16_t, bf16_t>(a, s);
     else if (ib) launch_s128_bwd<bf16_t, float>(a, s);
@@ -986,12 +1019,14 @@ void hamt_attn16_bwd_launch(const hamt_attn_desc* d, const void* q, const void* 
     return;
   }
   if (use_wide_bwd(d)) {
-    if (!ib && !ob) launch_wide_bwd<float, float>(a, s);
-    else if (ib && ob) launch_wide_bwd<bf16_t, bf16_t>(a, s);
-    else if (ib) launch_wide_bwd<bf16_t, float>(a, s);
-    else launch_wide_bwd<float, bf16_t>(a, s);
+    hamt_set_last_kernel("attn_wide_bwd_kernel");
+    if (!ib && !ob) launch_wide_bwd<float, float, false>(a, s);
+    else if (ib && ob) launch_wide_bwd<bf16_t, bf16_t, false>(a, s);
+    else if (ib) launch_wide_bwd<bf16_t, float, false>(a, s);
+    else launch_wide_bwd<float, bf16_t, false>(a, s);
     return;
   }
+  hamt_set_last_kernel("attn16_bwd_kernel");
   if (!ib && !ob) hipLaunchKernelGGL((attn16_bwd_kernel<float, float>), grid, block, 0, s, a);
   else if (ib && ob) hipLaunchKernelGGL((attn16_bwd_kernel<bf16_t, bf16_t>), grid, block, 0, s, a);
   else if (ib) hipLaunchKernelGGL((attn16_bwd_kernel<bf16_t, float>), grid, block, 0, s, a);

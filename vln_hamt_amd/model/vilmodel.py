@@ -304,7 +304,13 @@ def _ffn(inter, out, x, training):
 X_PACK = os.environ.get("HAMT_NO_X_PACK") != "1"
 # the side of the LAST cross-modal layer whose output the task head does not read is not computed (LXRTXLayer.forward `need`); HAMT_NO_DCE=1: always both
 DEAD_SIDE_ELIMINATION = os.environ.get("HAMT_NO_DCE") is None
-PACK_MAX_LEN = 128      # longest sequence hamt_attn_varlen_* / hamt_attn_varlen_cross_* serve (include/hamt.h)
+# The longest sequence (instruction tokens, and history + observation tokens on the other side of the cross attention) that runs packed;
+# a longer one goes back to the padded kernels.  hamt_attn_varlen_* / hamt_attn_varlen_cross_* serve 256 (include/hamt.h); 128 keeps every
+# packed backward on attn_s128_bwd_kernel.  HAMT_PACK_MAX_LEN=256 admits RxR's 250-token instructions (read here, at import; tests set the
+# global): whether packing wins there is a measurement, see DESIGN.md.
+PACK_MAX_LEN = int(os.environ.get("HAMT_PACK_MAX_LEN", "128"))
+if PACK_MAX_LEN not in (128, 256):
+    raise ValueError(f"HAMT_PACK_MAX_LEN={PACK_MAX_LEN}: 128 or 256")
 
 
 def _rows_of(x, rows):
@@ -441,8 +447,8 @@ class LxmertEncoder(nn.Module):
             vis = torch.cat([hist_embeds, img_embeds], 1)
             vis_masks = torch.cat([extended_hist_masks, extended_img_masks], -1)
         if unpack is not None and vis.size(1) > PACK_MAX_LEN:
-            # more visual tokens than the packed cross attention holds per sample (candidate views on top of the panorama): back to the
-            # padded layout in front of the cross-modal layers
+            # more visual tokens than the packed cross attention takes per sample under the limit (candidate views on top of the
+            # panorama): back to the padded layout in front of the cross-modal layers
             txt_embeds = ops.gather_rows(txt_embeds, unpack[0]).view(unpack[1], unpack[2], -1)
             unpack = None
         last = len(self.x_layers) - 1
@@ -602,8 +608,9 @@ class NavPreTrainedModel(BertPreTrainedModel):
         keys and nothing reads what they produce as queries (the reference computes them and throws them away)."""
         pack = getattr(txt_ids, "_hamt_pack", None)
         H = self.config.hidden_size      # (no parameter is touched here: optim.AdamW.attach's read gates sit in the child modules)
-        # (the packed attention kernels hold one sequence per workgroup: instructions of up to 128 tokens -- R2R's 80; RxR pretraining
-        # pads to 250, config/pretrain_rxr.json: such batches take the padded kernels, which serve up to 256 keys)
+        # (the packed attention kernels hold one sequence per workgroup: instructions of up to PACK_MAX_LEN tokens -- R2R's 80; RxR
+        # pretraining pads to 250, config/pretrain_rxr.json: at the default limit such batches take the padded kernels, which serve up
+        # to 256 keys)
         if pack is None or txt_ids.shape[1] > PACK_MAX_LEN or not (blocks.ENABLED and precision_of(self.config) == "bf16" and txt_ids.is_cuda and H % 64 == 0):
             x = self.embeddings(txt_ids)
             for layer in self.encoder.layer:
