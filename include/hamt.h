@@ -888,6 +888,28 @@ int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p16, float* 
                       const float* hyp, const float* rl, int nparams, float* partials, float* stats, const float* gnorm_sq,
                       float max_norm, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
                       int zero_grad, void* stream);
+/* The three passes of hamt_ralamb_table as calls of their own, passes 1 and 3 over the items [item_first, item_first + item_count)
+ * only (p, g, m, v, p16, slow, partials point at the START of their arenas: the item table holds arena offsets; `items`, `hyp`, `rl`
+ * still describe the whole arena): a rank of a sharded optimizer runs them over the items it owns (parallel.ShardedItemSync) and
+ * hamt_ralamb_trust over all parameters, once the ranks have summed their partial slots.
+ *   hamt_ralamb_moments_items: m, v (and g where it is zeroed) of the range's items and the partial slots of exactly those items.
+ *   hamt_ralamb_trust: stats of every active parameter from all nitems partial slots, in the fixed order of hamt_ralamb_table.
+ *   hamt_ralamb_apply_items: p, slow and p16 of the range's items, with the trust ratios in `stats`.
+ * Nothing outside the range's items' elements and partial slots is read or written (the tables apart), and an item's result does not
+ * depend on the range it is run in: disjoint item ranges that cover [0, nitems), in any order, with hamt_ralamb_trust between the last
+ * moments call and the first apply call, give bit for bit what one hamt_ralamb_table launch gives with the same item table
+ * (tests/test_gpu_ralamb_items.py::test_union_of_item_ranges_is_the_whole).  A range that does not lie inside [0, nitems], a NULL arena
+ * or table and a misaligned one are HAMT_ERR_ARG and nothing is launched; item_count == 0 is HAMT_OK and launches nothing.  The item
+ * table may cut a parameter into more items than 1024-float4 chunking needs (optim.rangerlars.item_table `cuts`): no item straddles a
+ * boundary between two owners. */
+int hamt_ralamb_moments_items(float* p, float* g, float* m, float* v, const int* items, int nitems, int item_first, int item_count,
+                              const float* hyp, const float* rl, int nparams, float* partials, const float* gnorm_sq, float max_norm,
+                              float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, int zero_grad,
+                              void* stream);
+int hamt_ralamb_trust(const int* items, int nitems, const float* hyp, int nparams, const float* partials, float* stats, void* stream);
+int hamt_ralamb_apply_items(float* p, const float* m, const float* v, void* p16, float* slow, const int* items, int nitems,
+                            int item_first, int item_count, const float* hyp, const float* rl, int nparams, const float* stats,
+                            float eps, void* stream);
 /* torch.optim's AdamW / Adam / RMSprop (momentum 0, not centered) / SGD (momentum 0): the finetune agents' optimisers
  * (finetune_src/r2r/agent_cmt.py:62-77), one launch over the whole arena with hamt_adamw_table's `ends` table, flags, clip and sweep.
  * Per element, gg = g * min(1, max_norm / (sqrt(*gnorm_sq) + 1e-6)) (1 when gnorm_sq is NULL or max_norm <= 0), t the parameter's own step:

@@ -195,6 +195,9 @@ SIGNATURES = {
     "hamt_adamw_table": [sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_adamw_table_range": [sz, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_ralamb_table": [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp],
+    "hamt_ralamb_moments_items": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, f32, f32, f32, f32, f32, f32, i32, vp],
+    "hamt_ralamb_trust": [vp, i32, vp, i32, vp, vp, vp],
+    "hamt_ralamb_apply_items": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, f32, vp],
     "hamt_optim_table": [i32, sz, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, f32, f32, f32, i32, vp],
     "hamt_clip_scale": [sz, vp, vp, f32, vp],
     "hamt_rng_advance": [vp, vp],

@@ -545,13 +545,15 @@ __global__ __launch_bounds__(256) void ralamb_moments_kernel(const float* __rest
                                                              float* __restrict__ v, const int* __restrict__ items, int nitems,
                                                              const float4* __restrict__ hyp, const float4* __restrict__ rl,
                                                              const float* __restrict__ gnorm_sq, float max_norm, float b1, float b2,
-                                                             float omb1, float omb2, float eps, int zero_grad, float2* __restrict__ partials) {
+                                                             float omb1, float omb2, float eps, int zero_grad, float2* __restrict__ partials,
+                                                             int item_first, int item_count) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   const RalambCoef c{clip_coef(gnorm_sq, max_norm), b1, b2, omb1, omb2, eps};
   const int* item_param = items + nitems + 1;
+  const int item_end = item_first + item_count;     // the launch's items [item_first, item_end): nothing of any other item is touched
   __shared__ float red[2][4][2];
   int par = 0;
-  for (int j = blockIdx.x; j < nitems; j += gridDim.x) {
+  for (int j = item_first + blockIdx.x; j < item_end; j += gridDim.x) {
     const int q = item_param[j];
     const float4 h = hyp[q];
     if (h.w == 0.f) continue;                       // (uniform over the block: no barrier is skipped by part of it)
@@ -615,10 +617,11 @@ __global__ __launch_bounds__(256) void ralamb_trust_kernel(const int* __restrict
 __global__ __launch_bounds__(256) void ralamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
                                                            bf16_t* __restrict__ p16, float* __restrict__ slow, const int* __restrict__ items,
                                                            int nitems, const float4* __restrict__ hyp, const float4* __restrict__ rl,
-                                                           const float4* __restrict__ stats, float eps) {
+                                                           const float4* __restrict__ stats, float eps, int item_first, int item_count) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   const int* item_param = items + nitems + 1;
-  for (int j = blockIdx.x; j < nitems; j += gridDim.x) {
+  const int item_end = item_first + item_count;
+  for (int j = item_first + blockIdx.x; j < item_end; j += gridDim.x) {
     const int q = item_param[j];
     const float4 h = hyp[q];
     if (h.w == 0.f) continue;
@@ -656,6 +659,55 @@ __global__ __launch_bounds__(256) void ralamb_apply_kernel(float* __restrict__ p
 
 }  // namespace
 
+// The three passes as entry points of their own: a rank of a sharded optimizer (parallel.ShardedItemSync) runs passes 1 and 3 over the
+// items it owns and pass 2 over all parameters, once the ranks have summed their partial slots.  The grid sweeps the launch's items
+// as the whole-table launch sweeps all of them; a partial is a block reduction of a fixed shape, so an item's result does not depend
+// on the range it is run in.
+static inline bool ralamb_item_range_ok(int nitems, int item_first, int item_count) {
+  return nitems > 0 && item_first >= 0 && item_count >= 0 && item_first <= nitems && item_count <= nitems - item_first;
+}
+extern "C" int hamt_ralamb_moments_items(float* p, float* g, float* m, float* v, const int* items, int nitems, int item_first,
+                                         int item_count, const float* hyp, const float* rl, int nparams, float* partials,
+                                         const float* gnorm_sq, float max_norm, float beta1, float beta2, float one_minus_beta1,
+                                         float one_minus_beta2, float eps, int zero_grad, void* stream) {
+  HAMT_CHECK_ARG(p && g && m && v && items && hyp && rl && partials && nparams > 0 && ralamb_item_range_ok(nitems, item_first, item_count),
+                 "hamt_ralamb_moments_items: bad argument (a NULL arena or table, or an item range outside [0, nitems])");
+  HAMT_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)g % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 &&
+                 ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)rl % 16) == 0 && ((uintptr_t)partials % 8) == 0,
+                 "hamt_ralamb_moments_items: arenas / tables must be 16-byte aligned (partials 8)");
+  if (item_count == 0) return HAMT_OK;
+  const int nb = item_count < 2048 ? item_count : 2048;     // (the grid sweeps the items together: see adamw_table_kernel)
+  hipLaunchKernelGGL(ralamb_moments_kernel, dim3(nb), dim3(256), 0, as_stream(stream), p, g, m, v, items, nitems, (const float4*)hyp,
+                     (const float4*)rl, gnorm_sq, max_norm, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, zero_grad,
+                     (float2*)partials, item_first, item_count);
+  HAMT_CHECK_LAUNCH("hamt_ralamb_moments_items");
+  return HAMT_OK;
+}
+extern "C" int hamt_ralamb_trust(const int* items, int nitems, const float* hyp, int nparams, const float* partials, float* stats,
+                                 void* stream) {
+  HAMT_CHECK_ARG(items && hyp && partials && stats && nitems > 0 && nparams > 0, "hamt_ralamb_trust: bad argument");
+  HAMT_CHECK_ARG(((uintptr_t)hyp % 16) == 0 && ((uintptr_t)stats % 16) == 0 && ((uintptr_t)partials % 8) == 0,
+                 "hamt_ralamb_trust: tables must be 16-byte aligned (partials 8)");
+  hipLaunchKernelGGL(ralamb_trust_kernel, dim3((nparams + 3) / 4), dim3(256), 0, as_stream(stream), items, nitems, (const float4*)hyp,
+                     nparams, (const float2*)partials, (float4*)stats);
+  HAMT_CHECK_LAUNCH("hamt_ralamb_trust");
+  return HAMT_OK;
+}
+extern "C" int hamt_ralamb_apply_items(float* p, const float* m, const float* v, void* p16, float* slow, const int* items, int nitems,
+                                       int item_first, int item_count, const float* hyp, const float* rl, int nparams,
+                                       const float* stats, float eps, void* stream) {
+  HAMT_CHECK_ARG(p && m && v && items && hyp && rl && stats && nparams > 0 && ralamb_item_range_ok(nitems, item_first, item_count),
+                 "hamt_ralamb_apply_items: bad argument (a NULL arena or table, or an item range outside [0, nitems])");
+  HAMT_CHECK_ARG(((uintptr_t)p % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)slow % 16) == 0 &&
+                 ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)rl % 16) == 0 && ((uintptr_t)stats % 16) == 0,
+                 "hamt_ralamb_apply_items: arenas / tables must be 16-byte aligned");
+  if (item_count == 0) return HAMT_OK;
+  const int nb = item_count < 2048 ? item_count : 2048;
+  hipLaunchKernelGGL(ralamb_apply_kernel, dim3(nb), dim3(256), 0, as_stream(stream), p, m, v, (bf16_t*)p16, slow, items, nitems,
+                     (const float4*)hyp, (const float4*)rl, (const float4*)stats, eps, item_first, item_count);
+  HAMT_CHECK_LAUNCH("hamt_ralamb_apply_items");
+  return HAMT_OK;
+}
 extern "C" int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p16, float* slow, const int* items, int nitems,
                                  const float* hyp, const float* rl, int nparams, float* partials, float* stats, const float* gnorm_sq,
                                  float max_norm, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
@@ -665,14 +717,10 @@ extern "C" int hamt_ralamb_table(float* p, float* g, float* m, float* v, void* p
                  ((uintptr_t)slow % 16) == 0 && ((uintptr_t)p16 % 8) == 0 && ((uintptr_t)hyp % 16) == 0 && ((uintptr_t)rl % 16) == 0 &&
                  ((uintptr_t)stats % 16) == 0 && ((uintptr_t)partials % 8) == 0,
                  "hamt_ralamb_table: arenas / tables must be 16-byte aligned (partials 8)");
-  hipStream_t s = as_stream(stream);
-  const int nb = nitems < 2048 ? nitems : 2048;     // (the grid sweeps the items together: see adamw_table_kernel)
-  hipLaunchKernelGGL(ralamb_moments_kernel, dim3(nb), dim3(256), 0, s, p, g, m, v, items, nitems, (const float4*)hyp, (const float4*)rl,
-                     gnorm_sq, max_norm, beta1, beta2, one_minus_beta1, one_minus_beta2, eps, zero_grad, (float2*)partials);
-  hipLaunchKernelGGL(ralamb_trust_kernel, dim3((nparams + 3) / 4), dim3(256), 0, s, items, nitems, (const float4*)hyp, nparams,
-                     (const float2*)partials, (float4*)stats);
-  hipLaunchKernelGGL(ralamb_apply_kernel, dim3(nb), dim3(256), 0, s, p, m, v, (bf16_t*)p16, slow, items, nitems, (const float4*)hyp,
-                     (const float4*)rl, (const float4*)stats, eps);
-  HAMT_CHECK_LAUNCH("hamt_ralamb_table");
-  return HAMT_OK;
+  // every argument is checked above, before the first launch: the three calls cannot refuse after one of them has run
+  int rc = hamt_ralamb_moments_items(p, g, m, v, items, nitems, 0, nitems, hyp, rl, nparams, partials, gnorm_sq, max_norm, beta1, beta2,
+                                     one_minus_beta1, one_minus_beta2, eps, zero_grad, stream);
+  if (rc == HAMT_OK) rc = hamt_ralamb_trust(items, nitems, hyp, nparams, partials, stats, stream);
+  if (rc == HAMT_OK) rc = hamt_ralamb_apply_items(p, m, v, p16, slow, items, nitems, 0, nitems, hyp, rl, nparams, stats, eps, stream);
+  return rc;
 }

@@ -8,7 +8,9 @@ sync.  The host keeps:
   * the arena's first table {lr, s*lr, weight_decay, active} (s: the RAdam step size, float64 like the reference's Python
     scalars) -- the gradient-norm kernels and parallel.py read its column 3;
   * a second table {N_sma >= 5, Lookahead action (0 none, 1 create, 2 interpolate), alpha, -weight_decay*lr};
-  * a static item table (each item inside one parameter, at most 4096 elements, in arena order) with one partial slot per item;
+  * a static item table (each item inside one parameter, at most 4096 elements, in arena order) with one partial slot per item
+    (`set_item_cuts`: also inside one owner's share of a sharded update -- parallel.ShardedItemSync runs passes 1 and 3 over the
+    items a rank owns, sums the partial slots over the ranks and runs pass 2 everywhere);
   * one more fp32 arena for the slow weights (RangerLars only).
 
 The reference's quirks are kept: the step count advances only for parameters with a gradient (ralamb.py:24, 51), weight decay is
@@ -43,18 +45,49 @@ def ralamb_coef(step: int, beta1: float, beta2: float):
     return False, 1.0 / (1 - beta1 ** step)
 
 
-def item_table(ends: np.ndarray, n: int) -> np.ndarray:
-    """The static item table of hamt_ralamb_table (include/hamt.h) for parameters ending at `ends` (elements, exclusive)."""
+def item_table(ends: np.ndarray, n: int, cuts=()) -> np.ndarray:
+    """The static item table of hamt_ralamb_table (include/hamt.h) for parameters ending at `ends` (elements, exclusive).  `cuts`:
+    element offsets (multiples of 8) that no item may straddle -- the boundaries between the owners of a sharded update
+    (parallel.ShardedItemSync): an item that would straddle one ends there and the next begins there."""
     ends4 = np.asarray(ends, dtype=np.int64) // 4
-    begins4 = np.concatenate([[0], ends4[:-1]])
-    counts = -(-(ends4 - begins4) // ITEM4)
-    first = np.concatenate([[0], np.cumsum(counts)])
-    nitems = int(first[-1])
-    param = np.repeat(np.arange(len(ends4)), counts)
-    starts = begins4[param] + (np.arange(nitems) - first[param]) * ITEM4
+    cuts = np.asarray(sorted(set(int(c) for c in cuts)), dtype=np.int64)
+    if cuts.size and ((cuts % 8).any() or cuts[0] < 0 or cuts[-1] > n):
+        raise ValueError(f"item_table: cuts must be multiples of 8 inside [0, {n}]")
+    # segments: the stretches between neighbouring breaks (parameter ends and cuts); each lies inside one parameter and one cut interval
+    breaks = np.unique(np.concatenate([[0], ends4, cuts // 4]))
+    lo4, hi4 = breaks[:-1], breaks[1:]
+    seg_param = np.searchsorted(ends4, lo4, side="right")             # the parameter q with begin(q) <= lo < end(q)
+    counts = -(-(hi4 - lo4) // ITEM4)
+    seg_first = np.concatenate([[0], np.cumsum(counts)])
+    nitems = int(seg_first[-1])
+    seg = np.repeat(np.arange(len(lo4)), counts)
+    starts = lo4[seg] + (np.arange(nitems) - seg_first[seg]) * ITEM4
+    param = seg_param[seg]
+    first = np.concatenate([[0], np.cumsum(np.bincount(param, minlength=len(ends4)))])
     tab = np.concatenate([starts, [n // 4], param, first]).astype(np.int64)
     assert tab.max() < 2 ** 31
     return tab.astype(np.int32), nitems
+
+
+def owned_item_runs(tab: np.ndarray, nitems: int, segments) -> list:
+    """[(item_first, item_count)]: the maximal runs of consecutive items of the table `tab` that lie inside the element segments
+    [(first, count)] (in arena order, as parallel.ShardedGradSync.owned() gives them).  Every segment boundary must be an item
+    boundary (a cut the table was built with): an item that straddles one has no single owner."""
+    starts = np.asarray(tab[:nitems + 1], dtype=np.int64)
+    runs = []
+    for f, c in segments:
+        if f % 4 or c % 4:
+            raise ValueError(f"owned_item_runs: segment ({f}, {c}) is not made of whole float4")
+        i0, i1 = int(np.searchsorted(starts, f // 4)), int(np.searchsorted(starts, (f + c) // 4))
+        if i1 > nitems or starts[i0] != f // 4 or starts[i1] != (f + c) // 4:
+            raise ValueError(f"owned_item_runs: an item straddles a boundary of the segment ({f}, {c}): build the item table with that cut")
+        if i1 == i0:
+            continue
+        if runs and runs[-1][0] + runs[-1][1] == i0:
+            runs[-1] = (runs[-1][0], runs[-1][1] + i1 - i0)
+        else:
+            runs.append((i0, i1 - i0))
+    return runs
 
 
 class Ralamb(ArenaOptimizer):
@@ -63,6 +96,7 @@ class Ralamb(ArenaOptimizer):
     _lookahead = False
     n_tables = 2                    # the arena's {lr, s*lr, weight_decay, active} and _rl
     no_range_reason = "every parameter's trust ratio needs its whole norm first"
+    item_slice_update = True        # the three passes run over item ranges (hamt_ralamb_*_items): parallel.ShardedItemSync asks for this
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         check_adam_args(lr, betas, eps)
@@ -73,14 +107,36 @@ class Ralamb(ArenaOptimizer):
     def _build(self):
         super()._build()
         n, dev, np_ = self._n, self._flat_p.device, len(self._params)
-        ends = self._ends.cpu().numpy()
-        tab, self._nitems = item_table(ends, n)
-        self._items = torch.from_numpy(tab).to(dev)
-        self._partials = torch.zeros(2 * self._nitems, dtype=torch.float32, device=dev)
+        self._item_cuts = ()
+        self._build_items()
         self._stats = torch.zeros(np_, 4, dtype=torch.float32, device=dev)     # {weight_norm, adam_norm, trust_ratio, 0}
         self._rl = self._tables[1]
         self._flat_slow = torch.zeros_like(self._flat_p) if self._lookahead else None
         self._has_slow = np.zeros(np_, dtype=bool)
+
+    def _build_items(self):
+        tab, self._nitems = item_table(self._ends.cpu().numpy(), self._n, self._item_cuts)
+        self._items_np = tab
+        self._items = torch.from_numpy(tab).to(self._flat_p.device)
+        self._partials = torch.zeros(2 * self._nitems, dtype=torch.float32, device=self._flat_p.device)
+
+    def set_item_cuts(self, cuts):
+        """Rebuild the item table (and its partial slots) so that no item straddles one of `cuts` (element offsets, multiples of 8):
+        what a sharded update needs at the boundaries between its owners.  Before the first step only: afterwards the table is
+        part of what the run computes (a parameter's norms are summed item by item), and changing it mid-run would change them."""
+        self.materialize()
+        cuts = tuple(sorted(set(int(c) for c in cuts)))
+        if cuts == self._item_cuts:
+            return
+        if self._steps.any() or self._counted is not None:
+            raise L.HamtError(f"{type(self).__name__}.set_item_cuts: the optimiser has stepped (or loaded a stepped state) with another item table; "
+                              "choose the exchange (parallel.make_grad_sync) before the first step and before load_state_dict")
+        self._item_cuts = cuts
+        self._build_items()
+
+    def item_runs(self, segments):
+        """the maximal runs of consecutive items inside the element segments [(first, count)]: `owned_item_runs` on this table"""
+        return owned_item_runs(self._items_np, self._nitems, segments)
 
     def _bytes_per_element(self, sync=False):
         """pass 1 reads p, g, m, v and writes m, v (24 per element), pass 3 reads p, m, v and writes p and the bf16 shadow (18),
@@ -121,6 +177,30 @@ class Ralamb(ArenaOptimizer):
                                            _p(slow) if slow is not None else None, _p(self._items), self._nitems, _p(self._hyp),
                                            _p(self._rl), len(self._params), _p(self._partials), _p(self._stats), gn, max_norm,
                                            b1, b2, 1 - b1, 1 - b2, g0["eps"], zero_grad_arena, _stream()), "hamt_ralamb_table")
+
+    # the three passes on their own, passes 1 and 3 over item runs [(item_first, item_count)]: the owned-item update of
+    # parallel.ShardedItemSync (static launches, capturable)
+    def launch_moments_items(self, runs, gn, max_norm, zero_grad_arena=True):
+        g0 = self.param_groups[0]
+        b1, b2 = g0["betas"]
+        lib = L.load()
+        for f, c in runs:
+            L.check(lib.hamt_ralamb_moments_items(_p(self._flat_p), _p(self._flat_g), _p(self._flat_m), _p(self._flat_v), _p(self._items),
+                                                  self._nitems, f, c, _p(self._hyp), _p(self._rl), len(self._params), _p(self._partials),
+                                                  _p(gn), float(max_norm), b1, b2, 1 - b1, 1 - b2, g0["eps"], int(zero_grad_arena),
+                                                  _stream()), "hamt_ralamb_moments_items")
+
+    def launch_trust(self):
+        L.check(L.load().hamt_ralamb_trust(_p(self._items), self._nitems, _p(self._hyp), len(self._params), _p(self._partials),
+                                           _p(self._stats), _stream()), "hamt_ralamb_trust")
+
+    def launch_apply_items(self, runs):
+        slow, lib = self._flat_slow, L.load()
+        for f, c in runs:
+            L.check(lib.hamt_ralamb_apply_items(_p(self._flat_p), _p(self._flat_m), _p(self._flat_v), _p(self._flat_p16),
+                                                _p(slow) if slow is not None else None, _p(self._items), self._nitems, f, c, _p(self._hyp),
+                                                _p(self._rl), len(self._params), _p(self._stats), self.param_groups[0]["eps"], _stream()),
+                    "hamt_ralamb_apply_items")
 
     def _taken_back(self):
         if self._la_pending is not None:

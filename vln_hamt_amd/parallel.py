@@ -363,24 +363,37 @@ def shardable(optimizer, world: int) -> bool:
 def per_tensor_update(optimizer) -> bool:
     """Has the optimizer NO owned-slice update?  The sharded exchange updates arena ranges that cut through parameters: an update
     that needs every parameter's whole norm (optim.rangerlars: the trust ratio) or has no range form of its kernel
-    (optim.torch_rules) says so in its class (`owned_slice_update = False`) and takes the all-reduce exchange."""
+    (optim.torch_rules) says so in its class (`owned_slice_update = False`) and takes the all-reduce exchange (the former, on request,
+    ShardedItemSync: `item_slice_update`)."""
     return not getattr(optimizer, "owned_slice_update", True)
+
+
+def item_slice_update(optimizer) -> bool:
+    """Has the optimizer an update over the ITEMS a rank owns, with a partial-sum exchange in the middle (optim.rangerlars: the trust
+    ratio's norms are sums of per-item partials)?  ShardedItemSync asks for this; ShardedGradSync (ranges that cut through parameters at
+    any multiple of 8) still refuses such an optimizer."""
+    return per_tensor_update(optimizer) and bool(getattr(optimizer, "item_slice_update", False))
 
 
 def make_grad_sync(optimizer, prec: str = "bf16", n_groups: int = 4, wire: str | None = None, sharded: bool | None = None):
     """The gradient exchange for this process group: ShardedGradSync (reduce-scatter, owned-slice AdamW, all-gather) in bf16 mode
-    when the arenas split evenly over the ranks, else OverlappedGradSync (all-reduce, full AdamW on every rank).  A RangerLars
-    and the torch-rule optimizers of the finetune agents always get OverlappedGradSync (per_tensor_update)."""
+    when the arenas split evenly over the ranks, else OverlappedGradSync (all-reduce, full AdamW on every rank).  The torch-rule
+    optimizers of the finetune agents always get OverlappedGradSync (per_tensor_update).  So does a Ralamb / RangerLars by default;
+    `sharded=True`, or HAMT_SHARDED_RANGERLARS=1 in bf16 mode (the switch an unmodified script reaches through wrap_model), gives it
+    ShardedItemSync: the owned-item update with the partial-sum exchange."""
     wire = wire or default_wire(prec)
     world = dist.get_world_size() if dist.is_initialized() else 1
+    items = item_slice_update(optimizer)
     if sharded is None:
-        sharded = os.environ.get("HAMT_SHARDED", "1") != "0" and prec == "bf16" and not per_tensor_update(optimizer)
+        sharded = os.environ.get("HAMT_SHARDED", "1") != "0" and prec == "bf16" and (
+            os.environ.get("HAMT_SHARDED_RANGERLARS") == "1" if items else not per_tensor_update(optimizer))
     if sharded and not shardable(optimizer, world):
         import warnings
         warnings.warn(f"vln_hamt_amd.parallel: 8 x world size ({world}) does not divide the arena regions (multiples of 512 elements); "
                       "using the all-reduce exchange (OverlappedGradSync) instead of the sharded one")
         sharded = False
-    return (ShardedGradSync if sharded else OverlappedGradSync)(optimizer, n_groups=n_groups, wire=wire)
+    cls = (ShardedItemSync if items else ShardedGradSync) if sharded else OverlappedGradSync
+    return cls(optimizer, n_groups=n_groups, wire=wire)
 
 
 class ShardedGradSync(OverlappedGradSync):
@@ -404,8 +417,13 @@ class ShardedGradSync(OverlappedGradSync):
 
     sharded = True
 
+    @staticmethod
+    def _refuses(optimizer) -> bool:
+        """no update over this class's owned slices"""
+        return per_tensor_update(optimizer)
+
     def __init__(self, optimizer, n_groups: int = 4, wire: str = "fp32"):
-        if per_tensor_update(optimizer):
+        if self._refuses(optimizer):
             raise ValueError(f"ShardedGradSync: {type(optimizer).__name__} has no update over owned slices that cut through parameters (a "
                              "trust ratio needs each parameter's whole norm; the torch rules have no range kernel); use the all-reduce "
                              "exchange (OverlappedGradSync, which make_grad_sync picks)")
@@ -430,7 +448,7 @@ class ShardedGradSync(OverlappedGradSync):
         self._own16 = torch.empty(o._n // self.world + 8, dtype=torch.bfloat16, device=o._flat_g.device) if wire == "bf16" else None
         self._own32 = torch.empty(o._n // self.world + 8, dtype=torch.float32, device=o._flat_g.device)
         self._gsq = torch.zeros(1, dtype=torch.float32, device=o._flat_g.device)
-        self._upd = None                   # (norm graph, update graph, max_norm) once graph.GraphedTrainStep captured them
+        self._upd = None                   # (norm graph, the rule phases' replays, max_norm) once graph.GraphedTrainStep captured them
         self._unconsumed = False           # an exchange has run and update() has not consumed it yet
         self._norm_reduced = False         # global_norm() ran for the pending exchange
 
@@ -616,18 +634,30 @@ class ShardedGradSync(OverlappedGradSync):
                                                _p(o._flat_p16[f:f + c]), _p(o._ends), _p(o._hyp), len(o._params), _p(self._gsq), float(max_norm),
                                                b1, b2, o.param_groups[0]["eps"], 1, _stream()), "hamt_adamw_table_range")
 
+    def _rule_phases(self, max_norm: float):
+        """the rule's launch runs behind the norm, as callables; `_between_phases` runs between two of them (a collective: each run is
+        captured as a graph of its own)"""
+        return [lambda: self._launch_adamw(max_norm)]
+
+    def _between_phases(self):
+        pass
+
     def capture_update(self, max_norm: float, pool, stream, mode):
-        """graph.GraphedTrainStep: the two launch runs of `update` (norm partials; clip + AdamW) as captured graphs -- 2 x 9 launches
-        the host no longer issues one by one between the collectives of every step.  Everything they read is static (arena
+        """graph.GraphedTrainStep: the launch runs of `update` (norm partials; clip + the rule's update) as captured graphs -- 2 x 9
+        launches the host no longer issues one by one between the collectives of every step.  Everything they read is static (arena
         pointers, owned segments, the device hyper-parameter table)."""
         if self._upd is not None and self._upd[2] == float(max_norm):
             return
-        g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, pool=pool, stream=stream, capture_error_mode=mode):
             self._launch_sumsq()
-        with torch.cuda.graph(g2, pool=pool, stream=stream, capture_error_mode=mode):
-            self._launch_adamw(max_norm)
-        self._upd = (g1, g2, float(max_norm))
+        rule = []
+        for phase in self._rule_phases(max_norm):
+            g2 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g2, pool=pool, stream=stream, capture_error_mode=mode):
+                phase()
+            rule.append(g2.replay)
+        self._upd = (g1, rule, float(max_norm))
 
     @torch.no_grad()
     def global_norm(self) -> torch.Tensor:
@@ -661,10 +691,10 @@ class ShardedGradSync(OverlappedGradSync):
         if dist.is_initialized() and not DRY[0] and not norm_reduced:
             dist.all_reduce(self._gsq, op=dist.ReduceOp.SUM)          # 4 bytes: the global squared norm
         self._norm_reduced = False
-        if graphs is not None:
-            graphs[1].replay()
-        else:
-            self._launch_adamw(max_norm)
+        for i, phase in enumerate(graphs[1] if graphs is not None else self._rule_phases(max_norm)):
+            if i:
+                self._between_phases()
+            phase()
         n_a = o._n_shadow_only
         gov = o._gather_ov
         if gov is not None and not torch.cuda.is_current_stream_capturing() and os.environ.get("HAMT_NO_GATHER_OVERLAP") is None:
@@ -712,6 +742,70 @@ class ShardedGradSync(OverlappedGradSync):
         o._shard_stale = False
 
     gather_masters = gather_state          # (round-2 name)
+
+
+class ShardedItemSync(ShardedGradSync):
+    """The sharded exchange for an optimizer whose update needs every parameter's whole norm in its middle (optim.rangerlars: Ralamb's
+    trust ratio) and runs over ITEMS: everything of ShardedGradSync -- the static ranges, reduce-scatter, the owned chunks' share of the
+    gradient norm and its 4-byte all-reduce, the parameters' all-gathers, attach_gather, one exchange per update -- with the update
+
+        zero the partial slots -> moments + partials over the owned items (hamt_ralamb_moments_items)
+        -> ONE all-reduce(SUM) of the partial slots (2 floats per item)
+        -> trust ratios of all parameters on every rank (hamt_ralamb_trust) -> update + Lookahead sync over the owned items
+           (hamt_ralamb_apply_items)
+
+    At construction the optimizer's item table is rebuilt with every boundary of every rank's owned chunks as a cut: no item straddles
+    two owners, and the table (hence every norm's summation order) is a function of the arena layout and the world size alone, the
+    same on every rank.  Every slot is written by exactly one rank and zero on the others, so the sum is exact and independent of
+    the order the ranks arrive in: the trust ratios, `_stats`, are bit-identical on every rank without being exchanged, like the
+    host-side Lookahead bookkeeping.  exp_avg, exp_avg_sq, the fp32 masters of the GEMM-weight region and the slow weights are current
+    in the owned items only: `gather_state()` on EVERY rank before `state_dict()`."""
+
+    @staticmethod
+    def _refuses(optimizer) -> bool:
+        return not item_slice_update(optimizer)
+
+    def __init__(self, optimizer, n_groups: int = 4, wire: str = "fp32"):
+        super().__init__(optimizer, n_groups, wire)
+        o = self.opt
+        cuts = set()
+        for lo, hi in self._ranges:
+            c = (hi - lo) // self.world
+            cuts.update(lo + r * c for r in range(self.world + 1))
+        try:
+            o.set_item_cuts(cuts)
+        except Exception:
+            self.close()                       # (an optimiser that has stepped with another table: leave it as it was found)
+            raise
+        self._item_runs = o.item_runs(self.owned())
+
+    def _moments(self, max_norm: float):
+        self.opt._partials.zero_()
+        self.opt.launch_moments_items(self._item_runs, self._gsq, max_norm, True)
+
+    def _trust_apply(self):
+        self.opt.launch_trust()
+        self.opt.launch_apply_items(self._item_runs)
+
+    def _rule_phases(self, max_norm: float):
+        return [lambda: self._moments(max_norm), self._trust_apply]
+
+    def _between_phases(self):
+        """every slot is non-zero on one rank at most: a plain sum (the same call under RCCL and gloo) is exact"""
+        if dist.is_initialized() and not DRY[0]:
+            dist.all_reduce(self.opt._partials, op=dist.ReduceOp.SUM)
+
+    @torch.no_grad()
+    def gather_state(self):
+        o = self.opt
+        slow = getattr(o, "_flat_slow", None)
+        if slow is not None:
+            o.wait_update()
+            for lo, hi in self._ranges:
+                self._all_gather_inplace(slow[lo:hi])
+        super().gather_state()
+
+    gather_masters = gather_state
 
 
 class ArenaDataParallel(torch.nn.Module):
