@@ -194,7 +194,8 @@ typedef struct {
 } hamt_wgrad_desc;
 /* `table`: caller-provided DEVICE scratch (16-byte aligned) that holds the launch table: HAMT_WGRAD_TABLE_ENTRY bytes per
  * entry, at most sum over the problems of ceil(M_p / 64) entries (large problems are cut into bands of tile rows); it is filled by small kernels from kernarg data, so `probs` need not outlive the call and the whole sequence can
- * be captured in a hipGraph.  The table must stay untouched until the launches have run. */
+ * be captured in a hipGraph.  The table must stay untouched until the launches have run.  Every requirement, the table's size
+ * included, is checked on the host before the first launch: a refused call has written nothing (tests/test_gpu_wgrad.py). */
 #define HAMT_WGRAD_TABLE_ENTRY 112
 int hamt_wgrad_grouped(int n, const hamt_wgrad_desc* probs, void* table, size_t table_bytes, void* stream);
 /* The same in two phases, for callers that replay a FIXED set of problems (a captured training step): phase 1 writes the launch table
@@ -522,10 +523,13 @@ int hamt_extend_mask(size_t n, const void* mask_u8, float* out, void* stream);
 int hamt_debug_fill_lds(uint32_t pattern, void* stream);
 /* measurement aid (bench.py `roofline`): with on != 0 every grouped weight-gradient KERNEL launched eagerly by
  * hamt_wgrad_grouped is bracketed by HIP events on its launch stream; hamt_debug_wgrad_times waits for them and returns
- * their number, writing up to `cap` durations (us), tile heights (256 = wgrad_grouped_p8_kernel) and flops (2 M N K over the
+ * their number, writing up to `cap` durations (us), tile heights (256 = a 256-square tile) and flops (2 M N K over the
  * launch's table, K = the k-tiles actually multiplied).  Not for captures. */
 int hamt_debug_wgrad_timing(int on);
 int hamt_debug_wgrad_times(float* us, int* tile_rows, double* flops, int cap);
+/* Which kernel each of those launches was: two_phase[i] = 1 for wgrad_grouped_p8_kernel (the two-phase 256-square tile), 0 for
+ * wgrad_grouped_kernel (64 / 128 rows, and the one-phase 256-square tile behind HAMT_WGRAD_P8=0).  Returns their number. */
+int hamt_debug_wgrad_variants(int* two_phase, int cap);
 /* dx = dy * act'(h): mode 1 erf-GELU (vilmodel.py:23-29), mode 2 ReLU (h may be the ReLU output) */
 int hamt_act_bwd(size_t n, const float* dy, const float* h, int mode, float* dx, void* stream);
 

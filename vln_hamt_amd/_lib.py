@@ -170,6 +170,7 @@ SIGNATURES = {
     "hamt_debug_fill_lds": [u32, vp],
     "hamt_debug_wgrad_timing": [C.c_int],
     "hamt_debug_wgrad_times": [vp, vp, vp, C.c_int],
+    "hamt_debug_wgrad_variants": [vp, C.c_int],
     "hamt_a2c_fwd": [i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp],
     "hamt_a2c_bwd": [i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp],
     "hamt_policy_step_fwd": [i32, i32, i32, i32, C.c_int64, vp, i32] + [vp] * 8 + [u32] + [vp] * 10,

@@ -1057,7 +1057,7 @@ static inline int kall(const hamt_wgrad_desc& d) { return keff(d) + keff2(d); }
 // Measurement aid for bench.py's `roofline` object: per-launch durations of the grouped weight-gradient kernels, taken with HIP
 // events recorded on the launch stream right around each kernel (not around the whole call: the table writes and the other tile
 // class are separate kernels in rocprofv3's summary too).  Eager launches only -- events cannot be read back from a capture.
-struct WgradTimed { hipEvent_t a, b; int bm; double flops; };
+struct WgradTimed { hipEvent_t a, b; int bm; double flops; int two_phase; };
 static bool wgrad_timing_on = false;
 static std::vector<WgradTimed> wgrad_timing_ev;
 extern "C" int hamt_debug_wgrad_timing(int on) {
@@ -1073,6 +1073,15 @@ extern "C" int hamt_debug_wgrad_times(float* us, int* tile_rows, double* flops, 
     float ms = 0.f;
     if (hipEventSynchronize(t.b) != hipSuccess || hipEventElapsedTime(&ms, t.a, t.b) != hipSuccess) return -1;
     if (n < cap) { if (us) us[n] = ms * 1e3f; if (tile_rows) tile_rows[n] = t.bm; if (flops) flops[n] = t.flops; }
+    ++n;
+  }
+  return n;
+}
+// two_phase[i] of the same launches: 1 = wgrad_grouped_p8_kernel, 0 = wgrad_grouped_kernel (any tile size; the 256-square one behind HAMT_WGRAD_P8=0)
+extern "C" int hamt_debug_wgrad_variants(int* two_phase, int cap) {
+  int n = 0;
+  for (auto& t : wgrad_timing_ev) {
+    if (n < cap && two_phase) two_phase[n] = t.two_phase;
     ++n;
   }
   return n;
@@ -1133,7 +1142,11 @@ static int wgrad_grouped_impl(int n, const hamt_wgrad_desc* probs, void* table, 
     if (force == 128 || force == 64 || (t256 < min256 && force != 256)) { cls[1].insert(cls[1].end(), cls[0].begin(), cls[0].end()); cls[0].clear(); }
   }
   WgradProb* tab = (WgradProb*)table;
-  int off = 0;
+  struct Unit { int prob, m_lo, m_rows, n_lo, n_cols, tiles; double cost; };
+  std::vector<Unit> cls_units[2];
+  int cls_bm[2] = {0, 0};
+  // First the host arithmetic of BOTH classes -- tile size and units -- so that a table too small for the call is refused before
+  // anything is launched (a refused call writes nothing), then the table writes and launches class by class.
   for (int c = 0; c < 2; ++c) {
     std::vector<int>& v = cls[c];
     if (v.empty()) continue;
@@ -1151,21 +1164,21 @@ static int wgrad_grouped_impl(int n, const hamt_wgrad_desc* probs, void* table, 
     // units: a problem, or rectangles of r x c tiles of a problem with many tiles (so that one XCD's share stays ~<= 12 tiles).  A unit's
     // tiles read r + c operand panels between them: the rectangle is the one that covers the problem with the fewest panel reads
     // (3 x 4 for the 3 x 12 tiles of an FFN-2 weight, where a row band reads 13 panels for its 12 tiles).
-    struct Unit { int prob, m_lo, m_rows, n_lo, n_cols, tiles; double cost; };
-    std::vector<Unit> units;
+    std::vector<Unit>& units = cls_units[c];
+    cls_bm[c] = bm;
     for (int i : v) {
       const hamt_wgrad_desc& d = probs[i];
       const int tm = (d.M + bm - 1) / bm, tn = (d.N + bn - 1) / bn;
       int ur = 1, uc = 1;
       long best = -1;
       for (int r = 1; r <= tm; ++r)
-        for (int c = 1; c <= tn; ++c) {
-          if (r * c > unit_tiles && !(r == 1 && c == tn)) continue;                                  // (a single tile row is always allowed)
-          if ((long)((tm + r - 1) / r) * ((tn + c - 1) / c) > (d.M + 63) / 64) continue;             // the caller's table: one entry per 64 output rows
+        for (int w = 1; w <= tn; ++w) {            // rectangles of r x w tiles
+          if (r * w > unit_tiles && !(r == 1 && w == tn)) continue;                                  // (a single tile row is always allowed)
+          if ((long)((tm + r - 1) / r) * ((tn + w - 1) / w) > (d.M + 63) / 64) continue;             // the caller's table: one entry per 64 output rows
           long panels = 0;                         // sum over the covering rectangles of (rows + columns)
           for (int r0 = 0; r0 < tm; r0 += r)
-            for (int c0 = 0; c0 < tn; c0 += c) panels += std::min(r, tm - r0) + std::min(c, tn - c0);
-          if (best < 0 || panels < best || (panels == best && r * c > ur * uc)) { best = panels; ur = r; uc = c; }
+            for (int c0 = 0; c0 < tn; c0 += w) panels += std::min(r, tm - r0) + std::min(w, tn - c0);
+          if (best < 0 || panels < best || (panels == best && r * w > ur * uc)) { best = panels; ur = r; uc = w; }
         }
       if (unit_2d == 0) { uc = tn; ur = tn >= unit_tiles ? 1 : unit_tiles / tn; }   // (row bands only: the round-2 placement, for measurements)
       for (int r0 = 0; r0 < tm; r0 += ur)
@@ -1176,6 +1189,14 @@ static int wgrad_grouped_impl(int n, const hamt_wgrad_desc* probs, void* table, 
         }
     }
     std::stable_sort(units.begin(), units.end(), [](const Unit& a, const Unit& b) { return a.cost > b.cost; });
+  }
+  HAMT_CHECK_ARG((cls_units[0].size() + cls_units[1].size()) * sizeof(WgradProb) <= table_bytes, "hamt_wgrad_grouped: table too small (%zu bytes needed)",
+                 (cls_units[0].size() + cls_units[1].size()) * sizeof(WgradProb));
+  int off = 0;
+  for (int c = 0; c < 2; ++c) {
+    const std::vector<Unit>& units = cls_units[c];
+    if (units.empty()) continue;
+    const int bm = cls_bm[c];
     std::vector<int> xq[8];
     double load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int u = 0; u < (int)units.size(); ++u) {           // longest processing time first onto the least loaded XCD
@@ -1185,8 +1206,6 @@ static int wgrad_grouped_impl(int n, const hamt_wgrad_desc* probs, void* table, 
       load[best] += units[u].cost;
     }
     const int cn = (int)units.size();
-    HAMT_CHECK_ARG((size_t)(off + cn) * sizeof(WgradProb) <= table_bytes, "hamt_wgrad_grouped: table too small (%zu bytes needed)",
-                   (size_t)(off + cn) * sizeof(WgradProb));
     WgradXcd xs;
     std::vector<WgradProb> flat;
     flat.reserve(cn);
@@ -1235,7 +1254,7 @@ static int wgrad_grouped_impl(int n, const hamt_wgrad_desc* probs, void* table, 
     else if (bm == 256) hipLaunchKernelGGL((wgrad_grouped_kernel<256, 256, 2, 4>), grid, dim3(512), 0, s, tab + off, xs);
     else if (bm == 128) hipLaunchKernelGGL((wgrad_grouped_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, tab + off, xs);
     else hipLaunchKernelGGL((wgrad_grouped_kernel<64, 128, 2, 2>), grid, dim3(256), 0, s, tab + off, xs);
-    if (ev0) { hipEventRecord(ev1, s); wgrad_timing_ev.push_back(WgradTimed{ev0, ev1, bm, launch_flops}); }
+    if (ev0) { hipEventRecord(ev1, s); wgrad_timing_ev.push_back(WgradTimed{ev0, ev1, bm, launch_flops, (bm == 256 && use_p8) ? 1 : 0}); }
     HAMT_CHECK_LAUNCH("hamt_wgrad_grouped");
     off += cn;
   }
